@@ -8,7 +8,10 @@ all-gather of the embeddings when N > 1) one global clustering.  Weak scaling: e
 shot boundaries) of one N x 1000-frame video.
 
 Prints ONE JSON line on rank 0 with `roofline` (dominant kernel = HOG filter scoring, HIP-event timed on the library's
-stream inside the timed region) and `cpu_baseline` (the CPU oracle on a bounded sample of the same frames, N = 1 only).
+stream inside the timed region).  A plain run sets up, warms up, times --steps steps and prints the line; `--full` adds what
+takes runs of its own: `cpu_baseline` (the CPU oracle on a bounded sample of the same frames, N = 1 only), the parity windows
+and the whole-clip fixture comparison, the dense-scoring, back-to-back, host-ingest and drop-in CLI legs, `other_configs`.
+`--dump-outputs DIR` writes the last timed step's result as DIR/<name>.npy.
 
 `--config` selects one of BASELINE.json's other configurations (the default, c2, is the one the metric is quoted on):
   c3  one long 1080p video streamed through the bounded-memory engine (configs[2]: --frames per rank, e.g. 22500 = 2 h / 8), frames
@@ -149,6 +152,40 @@ def labels_digest(labels):
     return hashlib.sha256(json.dumps(sorted((int(k), int(v)) for k, v in labels.items())).encode()).hexdigest()[:16]
 
 
+TRACK_STATUS = ("detection", "forward", "backward")
+DUMP_BYTES = 60 * 2 ** 20
+
+
+def dump_outputs(directory, results):
+    """--dump-outputs: what the last timed step handed its caller, one .npy per array, every clip's rows one after the other.
+      tracks      (clip, track, t, left, top, right, bottom, status: 0 detection / 1 forward / 2 backward) per track row
+      labels      (clip, track, cluster)
+      face_*      per embedded face: clip, time, track, box, 68 landmark points, 128-D descriptor; face_rows = their row numbers
+    Above DUMP_BYTES in all the faces are a fixed, seeded sample (the same rows for every array and every run)."""
+    import numpy as np
+    tracks = [(c, i, t) + tuple(box) + (TRACK_STATUS.index(s),) for c, (res, _) in enumerate(results)
+              for i, tr in enumerate(res["tracks"]) for t, box, s in tr]
+    labels = [(c, k, v) for c, (_, lab) in enumerate(results) for k, v in sorted(lab.items())]
+    out = {"tracks": np.array(tracks, np.float64).reshape(-1, 8), "labels": np.array(labels, np.float64).reshape(-1, 3)}
+    faces = {"face_clip": np.concatenate([np.full(len(res["face_T"]), c, np.float64) for c, (res, _) in enumerate(results)]),
+             "face_T": np.concatenate([np.asarray(res["face_T"], np.float64) for res, _ in results]),
+             "face_id": np.concatenate([np.asarray(res["face_id"], np.float64) for res, _ in results]),
+             "face_boxes": np.concatenate([np.asarray(res["face_boxes"], np.float64).reshape(-1, 4) for res, _ in results]),
+             "face_landmarks": np.concatenate([np.asarray(res["landmarks"], np.float32).reshape(-1, 68, 2) for res, _ in results]),
+             "face_embeddings": np.concatenate([np.asarray(res["embeddings"], np.float32).reshape(-1, 128) for res, _ in results])}
+    n = len(faces["face_T"])
+    rows = np.arange(n)
+    per_face = sum(a.nbytes for a in faces.values()) // max(n, 1) + 8
+    room = max(DUMP_BYTES - sum(a.nbytes for a in out.values()), 0) // max(per_face, 1)
+    if n > room:
+        rows = np.sort(np.random.default_rng(0).choice(n, room, replace=False))
+    out.update({k: a[rows] for k, a in faces.items()})
+    out["face_rows"] = rows.astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -190,9 +227,16 @@ def main():
                          "torch.distributed collectives: two ranks of one RCCL communicator cannot share a device).  Exercises the launcher, the "
                          "shot-range sharding, the gather and the global clustering; the line says `oversubscribed`: its value is NOT a scaling figure")
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port of the ranks this process launches (0: a free one)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, everything else the line can report: the dense-scoring leg, back-to-back clips, the "
+                    "whole-clip fixture comparison, the CPU-oracle baseline and parity windows, the host-ingest pass, the drop-in CLI verbs, the CPU-oracle "
+                    "cluster check and the other configurations (without it: set-up, warm-up, the timed steps and the headline figures only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned as DIR/<name>.npy (float32 / float64; "
+                    "seeded inputs, so two builds can be compared output for output)")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return launch_ranks(args)             # this process becomes the launcher: N ranks of this script, one per GPU
     if "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) != args.gpus:
@@ -345,6 +389,8 @@ def main():
                 "faces": int(len(res["face_T"])), "last_step_s": {k: round(float(tm.get(k, 0.0)), 4) for k in ("track_s", "extract_s", "exchange_s", "cluster_s", "step_wall_s")}}
         per_rank = [None] * world
         tdist.all_gather_object(per_rank, mine)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [(res, labels)])
     if os.environ.get("PVF_DUMP") and rank == 0:
         ident_of_track = {}
         np.savez_compressed(os.environ["PVF_DUMP"], X=res["X"], emb=res["embeddings"], face_id=res["face_id"], face_T=res["face_T"],
@@ -379,7 +425,7 @@ def main():
     # the same steps with the screening pass off (the exact fp32 chain for every window): what the screening buys, that the results are
     # the same, and the dense kernel's own roofline -- two timed steps after one untimed
     dense = None
-    if world == 1 and not args.dense_scoring and not args.no_dense_leg and args.detect_every == 0.0:
+    if args.full and world == 1 and not args.dense_scoring and not args.no_dense_leg and args.detect_every == 0.0:
         ctx.detector_screening(False)
         step()
         ctx.prof_reset(); ctx.prof_enable(True)
@@ -405,7 +451,7 @@ def main():
     # assembly before the next step's first kernel -- and a deployment that has the next video waiting does not pay that drain.  NOT
     # `value` (whose steps run one after the other, each complete before the next starts); outside the timed region.
     back_to_back = None
-    if world == 1 and not args.dense_scoring and not args.no_dense_leg and args.detect_every == 0.0 and args.config == "c2":
+    if args.full and world == 1 and not args.dense_scoring and not args.no_dense_leg and args.detect_every == 0.0 and args.config == "c2":
         clips = [dict(frames=frames, times=times, frame_rate=video.frame_rate, shots=shots) for _ in range(4)]
         pipe.run_many(clips)
         barrier()
@@ -425,27 +471,27 @@ def main():
     # detector's raw candidates of every frame against the fixture the oracle flow wrote for all 1000 frames (tests/golden/c2_full.npz,
     # made by tests/golden/make_full_clip.py: minutes of CPU, so it is frozen, not recomputed here); the dense leg the same way
     full_clip = None
-    if world == 1 and args.detect_every == 0.0 and not args.small_models:
+    if args.full and world == 1 and args.detect_every == 0.0 and not args.small_models:
         # configs[1]: the whole clip; configs[4]: the clip's first shot (250 of its 500 4K frames: the oracle needs an hour for them)
         full_clip = full_clip_parity(ctx, frames, res, labels, args, d_res=d_res if dense else None, d_labels=d_labels if dense else None,
                                      name="c2_full" if args.config == "c2" else "c5_shot0")
 
     cpu, parity = None, None
-    if world == 1 and args.cpu_frames > 0:
+    if args.full and world == 1 and args.cpu_frames > 0:
         cpu, parity = cpu_baseline_and_parity(video, frames_t, ctx, pipe, lp, ep, args)
     if full_clip is not None:
         parity = dict(parity or {}, full_clip=full_clip)
         if cpu is not None:
             cpu["whole_clip_fixture"] = {k: full_clip.get(k) for k in ("fixture", "frames", "all_exact", "raw_candidates", "embed_l2_max", "oracle_seconds", "oracle_threads")}
     host = None
-    if world == 1 and not args.no_host_ingest and args.config == "c2":
+    if args.full and world == 1 and not args.no_host_ingest and args.config == "c2":
         host = host_ingest_pass(ctx, pipe, frames_t, times, video, shots, args)
     dropin = None
-    if world == 1 and not args.no_dropin and args.config == "c2" and args.detect_every == 0.0:
+    if args.full and world == 1 and not args.no_dropin and args.config == "c2" and args.detect_every == 0.0:
         dropin = dropin_cli_pass(ctx, frames, video, lp, ep, fps, res, labels)
 
     other = None
-    if (world == 1 and args.config == "c2" and not args.no_other_configs and not args.dense_scoring and not args.small_models and args.detect_every == 0.0
+    if (args.full and world == 1 and args.config == "c2" and not args.no_other_configs and not args.dense_scoring and not args.small_models and args.detect_every == 0.0
             and args.frames == 1000 and args.cpu_frames > 0):
         other = other_configs_pass(args)
 
@@ -499,7 +545,7 @@ def main():
         out["roofline"]["step_with_dense_scoring_frames_per_s"] = out["dense_scoring_value"]
         out["roofline"]["screening_listed_pairs_per_frame"] = out.get("listed_per_frame")
     # last key of the line (the driver keeps the line's tail verbatim): the whole-clip verdict in one short string
-    out["full_clip_parity"] = full_clip_summary(full_clip)
+    out["full_clip_parity"] = full_clip_summary(full_clip, args.full)
     if other is not None:
         out["full_clip_parity"] += " || other configs: " + "; ".join(("%s %s frames/s, %s" % (k, v.get("frames_per_s"), v.get("verdict"))) if v.get("frames_per_s") else ("%s: %s" % (k, v.get("verdict")))
                                                                         for k, v in other.items() if isinstance(v, dict))
@@ -518,7 +564,7 @@ def other_configs_pass(args):
     runs = [("c5_shot0", ["--config", "c5", "--steps", "2", "--warmup", "1"]),
             ("c4_8clips", ["--config", "c4", "--clips", "8", "--steps", "2", "--warmup", "1"]),
             ("c3_clip0", ["--config", "c3", "--frames", "1000", "--distinct-clips", "1", "--steps", "1", "--warmup", "1", "--cluster-check-frames", "0"])]
-    common = ["--gpus", "1", "--cpu-frames", "0", "--no-host-ingest", "--no-dropin", "--no-dense-leg", "--no-other-configs"]
+    common = ["--gpus", "1", "--full", "--cpu-frames", "0", "--no-host-ingest", "--no-dropin", "--no-dense-leg", "--no-other-configs"]
     out = {}
     t_all = time.perf_counter()
     for name, extra in runs:
@@ -598,7 +644,9 @@ def full_clip_parity(ctx, frames, res, labels, args, d_res=None, d_labels=None, 
     return out
 
 
-def full_clip_summary(fc):
+def full_clip_summary(fc, full=True):
+    if not full:
+        return "not compared (--full compares the run with its whole-clip fixture)"
     if not fc or not fc.get("fixture"):
         return "no whole-clip fixture for this configuration"
     if fc["all_exact"]:
@@ -835,13 +883,15 @@ def bench_farm(args, rank, local_rank, world, device, lp, ep):
         fam[name] = {"ms": round(ms, 3), "launches": int(n)}
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [(r, r["labels"]) for r in results])
     total_frames = args.clips * args.frames * args.steps
     fps = total_frames / elapsed
     geo = pipeline.detector_geometry(args.height, args.width)
     flop_per_frame = sum(g[4] for g in geo) * 3100 * 5 * 2.0
     rl = detector_rooflines(fam, args.height, args.width, len(mine) * args.frames * args.steps, args.detect_batch)
     parity, cpu = None, None
-    if args.cpu_frames > 0:
+    if args.full and args.cpu_frames > 0:
         # parity gate: clip 0, a window around its shot cut, product (frames resident) vs the CPU oracle flow
         v, ft = videos[0], tensors[0]
         n = min(16, v.n_frames)
@@ -854,7 +904,7 @@ def bench_farm(args, rank, local_rank, world, device, lp, ep):
         parity, dt, threads = oracle_window_parity([np.ascontiguousarray(ft[i].cpu().numpy()) for i in idx], times, shots, v.frame_rate, v.frame_size, res, lp, ep,
                                                    label="clip 0, frames %d..%d (a window around its cut), product vs CPU oracle flow" % (idx[0], idx[-1]))
         cpu = {"value": round(n / dt, 4), "unit": "frames/s", "cores": int(threads), "kind": "port", "sample": "the same %d-frame 720p window, whole flow" % n}
-    if rank == 0 and not args.dense_scoring and not args.small_models:
+    if args.full and rank == 0 and not args.dense_scoring and not args.small_models:
         # clip 0 (this rank's first) over ALL its frames against the fixture of the CPU oracle flow (tests/golden/c4_clip0.npz)
         fc = full_clip_parity(ctx, clips[0]["frames"], results[0], results[0]["labels"], args, name="c4_clip0", seed=20260925)
         parity = dict(parity or {}, full_clip=fc)
@@ -878,7 +928,7 @@ def bench_farm(args, rank, local_rank, world, device, lp, ep):
            "results": {"clips": len(results), "tracks": sum(len(r["tracks"]) for r in results), "faces_embedded": sum(int(len(r["face_T"])) for r in results),
                        "clusters_per_clip": [len(set(r["labels"].values())) for r in results][:8]},
            "setup_seconds": {"generate_frames_in_hbm": round(t_gen, 1)}}
-    out["full_clip_parity"] = full_clip_summary(fc)
+    out["full_clip_parity"] = full_clip_summary(fc, args.full)
     print(json.dumps(out))
 
 
@@ -976,12 +1026,14 @@ def bench_stream(args, rank, local_rank, world, device, lp, ep):
         fam[name] = {"ms": round(ms, 3), "launches": int(k)}
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [(res, labels)])
     fps = n * world * args.steps / elapsed
     geo = pipeline.detector_geometry(args.height, args.width)
     flop_per_frame = sum(g[4] for g in geo) * 3100 * 5 * 2.0
     rl = detector_rooflines(fam, args.height, args.width, n * args.steps, args.detect_batch)
     parity, cpu, cluster_check = None, None, None
-    if world == 1 and args.cpu_frames > 0:
+    if args.full and world == 1 and args.cpu_frames > 0:
         # parity gate through the STREAMING path: a window across the seam between two loops (last frames of one clip's last shot, first
         # frames of the next clip's first shot: a cut), product (run_stream, frames delivered one by one) vs the CPU oracle flow
         m = min(8, args.cpu_frames)
@@ -995,10 +1047,10 @@ def bench_stream(args, rank, local_rank, world, device, lp, ep):
         parity, dt, threads = oracle_window_parity(frames_np, times, wshots, args.fps, videos[0].frame_size, r, lp, ep,
                                                    label="frames %d..%d of the long video (across the seam between two clips: a cut), streamed product vs CPU oracle flow" % (idx[0], idx[-1]))
         cpu = {"value": round(m / dt, 4), "unit": "frames/s", "cores": int(threads), "kind": "port", "sample": "the same %d-frame window, whole flow" % m}
-    if world == 1 and args.cluster_check_frames != 0 and len(res["face_T"]):
+    if args.full and world == 1 and args.cluster_check_frames != 0 and len(res["face_T"]):
         cluster_check = oracle_cluster_check(pipe, res, args.cluster_check_frames / args.fps if args.cluster_check_frames > 0 else float("inf"))
     full_clip = None
-    if rank == 0 and first == 0 and n >= clip_n and not args.dense_scoring and not args.small_models:
+    if args.full and rank == 0 and first == 0 and n >= clip_n and not args.dense_scoring and not args.small_models:
         # the first 1000-frame clip of the long video, as the STREAMED run produced it, against the oracle flow's output over all its frames
         # (tests/golden/c3_clip0.npz); the raw-candidate pass runs on the clip's resident frames
         clip_frames = [ctx.wrap_torch(clips_t[0][i]) for i in range(clip_n)]
@@ -1028,7 +1080,7 @@ def bench_stream(args, rank, local_rank, world, device, lp, ep):
                        "tracks_clustered_globally": len(labels), "labels_sha256_16": labels_digest(labels),
                        "identities_in_video": len(idents)},
            "setup_seconds": {"generate_clips_in_hbm": round(t_gen, 1)}}
-    out["full_clip_parity"] = full_clip_summary(full_clip)
+    out["full_clip_parity"] = full_clip_summary(full_clip, args.full)
     print(json.dumps(out))
 
 

@@ -1,33 +1,51 @@
-"""Test infrastructure: runs the REFERENCE'S OWN Python, verbatim, from /root/reference, on top of a dlib look-alike.
+"""Test infrastructure: runs the REFERENCE'S OWN Python, verbatim, from a checkout of pyannote-video named by PVF_REFERENCE, on top
+of a dlib look-alike.
 
 The reference is pure Python; everything it computes goes through `dlib`, `munkres`, `networkx`, numpy and pandas
 (pyannote/video/tracking.py:31-35, face/face.py:30-32, scripts/pyannote-face.py:92-109).  None of its files is copied:
 they are executed where they lie, with
     sys.modules['dlib']     = the module under test (pyannote_video_amd.shim on a GPU, tests/oracle_dlib.py on CPU)
-    sys.modules['munkres']  = the real package (its source is on disk at /opt/conda/lib/python3.9/site-packages/munkres.py)
+    sys.modules['munkres']  = the real package (importable, or its munkres.py named by PVF_MUNKRES)
     `pyannote`, `pyannote.video`, `pyannote.video.face`, `pyannote.core`, `docopt`, `cv2` = empty / minimal stand-in modules,
       because pyannote/video/__init__.py would pull in ffmpeg / OpenCV code that is out of scope.
 This is exactly the "edit" INTEGRATION.md describes: the reference's host code stays, only `import dlib` is re-pointed.
 
-/root/reference exists in the build container only.  Tests that use this module skip when it is absent (GPU box); what they
-establish travels as committed fixtures under tests/golden/ (generated by tests/golden/make_reference_golden.py).
+The reference is not part of this repository.  What its code returns on the tests' seeded inputs is recorded where it is available
+(tests/golden/make_reference_golden.py, tests/golden/make_reference_pins.py) and travels as committed fixtures under tests/golden/,
+which the tests compare the product and the oracle with (`recorded`).
 """
 import contextlib
+import gzip
 import importlib.util
+import json
 import os
 import sys
 import types
 
-REFERENCE = "/root/reference"
-MUNKRES_PY = "/opt/conda/lib/python3.9/site-packages/munkres.py"
+REFERENCE = os.environ.get("PVF_REFERENCE", "")
+MUNKRES_PY = os.environ.get("PVF_MUNKRES", "")
+PINS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_pins.json.gz")
 
 
 def have_reference():
-    return os.path.isfile(os.path.join(REFERENCE, "pyannote", "video", "tracking.py"))
+    return bool(REFERENCE) and os.path.isfile(os.path.join(REFERENCE, "pyannote", "video", "tracking.py"))
 
 
 def have_munkres():
-    return os.path.isfile(MUNKRES_PY)
+    return importlib.util.find_spec("munkres") is not None or os.path.isfile(MUNKRES_PY)
+
+
+_pins = None
+
+
+def recorded(name):
+    """what the reference's code (or the real munkres package) returned for one test's seeded inputs: tests/golden/reference_pins.json.gz,
+    written by tests/golden/make_reference_pins.py"""
+    global _pins
+    if _pins is None:
+        with gzip.open(PINS, "rt") as f:
+            _pins = json.load(f)
+    return _pins[name]
 
 
 def _load(name, path, register=True):
@@ -43,12 +61,15 @@ _munkres = None
 
 
 def real_munkres():
-    """the munkres package itself (1.1.4), loaded from its source file"""
+    """the munkres package itself (1.1.4): the installed one, else loaded from its source file"""
     global _munkres
     if _munkres is None:
-        spec = importlib.util.spec_from_file_location("_real_munkres", MUNKRES_PY)
-        _munkres = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(_munkres)
+        if importlib.util.find_spec("munkres") is not None:
+            _munkres = importlib.import_module("munkres")
+        else:
+            spec = importlib.util.spec_from_file_location("_real_munkres", MUNKRES_PY)
+            _munkres = importlib.util.module_from_spec(spec)
+            spec.loader.exec_module(_munkres)
     return _munkres
 
 

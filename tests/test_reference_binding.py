@@ -33,16 +33,6 @@ def _clip():
     return v, [v.frame(i) for i in range(v.n_frames)], [v.timestamp(i) for i in range(v.n_frames)]
 
 
-@needs_reference
-def test_reference_cli_reproduces_the_committed_fixtures(tmp_path, model_paths):
-    import oracle_dlib
-    from pyannote_video_amd import models
-    oracle_dlib.configure(models.load_container(models.DEFAULT_DETECTOR), models.dsst_tables())
-    paths = mrg.run_reference_cli(str(tmp_path), oracle_dlib, model_paths[0], model_paths[1])
-    for p, name in zip(paths, ("track.txt", "landmarks.txt", "embedding.txt")):
-        assert _lines(p) == _lines(os.path.join(GOLD[0.0], name)), name
-
-
 @pytest.mark.parametrize("every", [0.0, 0.12])
 def test_sequential_restatement_equals_reference_cli_output(every, oracle, model_paths):
     """oracle/ref_flow.py (what the GPU parity tests compare with) == files the reference's own code wrote"""

@@ -1,9 +1,12 @@
-"""a7 / a9 pinned to the reference's own clustering.py, executed verbatim (its arithmetic is numpy / scipy / pandas, all installed):
+"""a7 / a9 pinned to the reference's own clustering.py, executed verbatim (its arithmetic is numpy / scipy / pandas):
 `_Model.preprocess` (track extents, skipped empty segments, row order), `compute_model`, `compute_similarity_matrix` (minus the mean of the
-|i| x |j| block of scipy's pdist) and `compute_similarity` of merged clusters, against the CPU oracle and the product's host code.
+|i| x |j| block of scipy's pdist) and `compute_similarity` of merged clusters, against the CPU oracle and the product's host code --
+through what the reference returned on these tests' seeded embedding files: tests/golden/reference_pins.json.gz
+(tests/golden/make_reference_pins.py runs `record` below where the reference is available).
 What stays unpinned is pyannote.algorithms' agglomeration loop (absent): see tests/refhost.reference_clustering_module."""
 import os
 import sys
+import tempfile
 import warnings
 
 import numpy as np
@@ -11,8 +14,6 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(__file__))
 import refhost  # noqa: E402
-
-pytestmark = pytest.mark.skipif(not refhost.have_reference(), reason="/root/reference is not present (GPU box)")
 
 
 def _embedding_file(tmp_path, seed, n_tracks=14, n_ident=4):
@@ -38,12 +39,23 @@ def _embedding_file(tmp_path, seed, n_tracks=14, n_ident=4):
     return path
 
 
-@pytest.mark.parametrize("seed", range(4))
-def test_reference_model_similarities_equal_oracle_and_product_host(tmp_path, seed):
-    from oracle import oracle
-    from pyannote_video_amd import clustering as mine
+def _features_record(data):
+    """the reference preprocess' DataFrame (rows sorted in place: the index keeps the file's row numbers)"""
+    return {"index": [int(i) for i in data.index], "time": data["time"].tolist(), "track": [int(t) for t in data["track"]],
+            "X": np.array(data[data.columns[2:]]).tolist()}
+
+
+def _features(rec):
+    """that DataFrame again, with the reference's column names and dtypes (clustering.py:71-76)"""
+    import pandas
+    cols = {"time": np.array(rec["time"], np.float64), "track": np.array(rec["track"], np.int64)}
+    X = np.array(rec["X"], np.float64)
+    cols.update(("d%d" % i, X[:, i]) for i in range(128))
+    return pandas.DataFrame(cols, index=rec["index"])
+
+
+def _reference_model_similarities(path):
     from pyannote_video_amd._core import Segment, Annotation
-    path = _embedding_file(tmp_path, seed)
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
         with refhost.reference_clustering_module(Segment, Annotation) as ref:
@@ -59,9 +71,24 @@ def test_reference_model_similarities_equal_oracle_and_product_host(tmp_path, se
             merged = np.hstack([model[tracks[0]], model[tracks[1]]])          # what compute_merged_model means (np.hstack of a generator
             model._models["m"] = merged                                         # no longer runs on numpy >= 2: SURVEY.md section 8 a9)
             sim_merged = float(model.compute_similarity("m", tracks[2]))
-            ref_rows = data[["time", "track"]].to_numpy()
-            ref_X = np.array(data[data.columns[2:]])
-            ref_start = sorted((s.start, s.end, int(t)) for s, t in starting_point.itertracks())
+            start = sorted((float(s.start), float(s.end), int(t)) for s, t in starting_point.itertracks())
+    return {"features": _features_record(data), "tracks": tracks, "start": start, "sim_merged": sim_merged,
+            "matrix": [[a, b, float(matrix[a, b])] for a in tracks for b in tracks if a != b]}
+
+
+@pytest.mark.parametrize("seed", range(4))
+def test_reference_model_similarities_equal_oracle_and_product_host(tmp_path, seed):
+    from oracle import oracle
+    from pyannote_video_amd import clustering as mine
+    path = _embedding_file(tmp_path, seed)
+    rec = refhost.recorded("clustering_model")[str(seed)]
+    data = _features(rec["features"])
+    tracks = rec["tracks"]
+    matrix = {(a, b): v for a, b, v in rec["matrix"]}
+    sim_merged = rec["sim_merged"]
+    ref_rows = data[["time", "track"]].to_numpy()
+    ref_X = np.array(data[data.columns[2:]])
+    ref_start = [tuple(x) for x in rec["start"]]
     # preprocess: same rows in the same (track, time) order, same starting point
     sp, feats = mine._Model().preprocess(path)
     assert np.array_equal(feats.time, ref_rows[:, 0]) and np.array_equal(feats.track, ref_rows[:, 1].astype(np.int64))
@@ -89,15 +116,9 @@ class _OracleContext(object):
         return oracle.pair_mean_dist(X, row_start)
 
 
-@pytest.mark.parametrize("seed", range(3))
-def test_product_hooks_drive_the_same_agglomeration_as_the_reference_hooks(tmp_path, seed):
-    """seam S5: the reference's `_Model` (executed verbatim) and the product's, each driven through the SAME average-linkage loop over
-    compute_model / compute_merged_model / compute_similarity_matrix / compute_similarity -- same models, same matrix (to 1e-12), same
-    merges, same labels, same return types."""
+def _reference_hooks(path):
     import hac_driver
-    from pyannote_video_amd import clustering as mine
     from pyannote_video_amd._core import Segment, Annotation
-    path = _embedding_file(tmp_path, 100 + seed, n_tracks=18, n_ident=5)
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
         with refhost.reference_clustering_module(Segment, Annotation) as ref:
@@ -107,6 +128,26 @@ def test_product_hooks_drive_the_same_agglomeration_as_the_reference_hooks(tmp_p
             first_model = model_r.compute_model(tracks[0], parent=hac_driver._Parent(data_r))
             labels_r, log_r = hac_driver.agglomerate(model_r, data_r, tracks, 0.6)
             matrix_type = type(ref.ValueSortedDict()).__mro__[1]
+    return {"features": _features_record(data_r), "tracks": tracks, "first_model": [int(i) for i in first_model],
+            "first_model_dtype": str(first_model.dtype), "labels": sorted([int(k), int(v)] for k, v in labels_r.items()),
+            "log": [[int(a), int(b), float(d)] for a, b, d in log_r], "matrix_type_is_dict": matrix_type is dict}
+
+
+@pytest.mark.parametrize("seed", range(3))
+def test_product_hooks_drive_the_same_agglomeration_as_the_reference_hooks(tmp_path, seed):
+    """seam S5: the reference's `_Model` (executed verbatim) and the product's, each driven through the SAME average-linkage loop over
+    compute_model / compute_merged_model / compute_similarity_matrix / compute_similarity -- same models, same matrix (to 1e-12), same
+    merges, same labels, same return types."""
+    import hac_driver
+    from pyannote_video_amd import clustering as mine
+    path = _embedding_file(tmp_path, 100 + seed, n_tracks=18, n_ident=5)
+    rec = refhost.recorded("clustering_hooks")[str(seed)]
+    data_r = _features(rec["features"])
+    tracks = rec["tracks"]
+    first_model = np.array(rec["first_model"], rec["first_model_dtype"])
+    labels_r = {k: v for k, v in rec["labels"]}
+    log_r = [tuple(x) for x in rec["log"]]
+    matrix_type = dict if rec["matrix_type_is_dict"] else None
     model_p = mine._Model(ctx=_OracleContext())
     sp_p, data_p = model_p.preprocess(path)
     assert tracks == sorted(int(t) for _, _, t in sp_p.itertracks(yield_label=True))
@@ -133,3 +174,16 @@ def test_product_hooks_drive_the_same_agglomeration_as_the_reference_hooks(tmp_p
     D = oracle.pair_mean_dist(data_p.X[np.concatenate(rows)], row_start)
     lab, _ = oracle.hac(D, np.diff(row_start), 0.6)
     assert [tracks[int(l)] for l in lab] == [labels_p[t] for t in tracks]
+
+
+def record():
+    """the fixture entries of this module, computed by the reference's clustering.py"""
+    out = {"clustering_model": {}, "clustering_hooks": {}}
+    d = tempfile.mkdtemp()
+    import pathlib
+    for seed in range(4):
+        out["clustering_model"][str(seed)] = _reference_model_similarities(_embedding_file(pathlib.Path(tempfile.mkdtemp(dir=d)), seed))
+    for seed in range(3):
+        out["clustering_hooks"][str(seed)] = _reference_hooks(_embedding_file(pathlib.Path(tempfile.mkdtemp(dir=d)), 100 + seed,
+                                                                              n_tracks=18, n_ident=5))
+    return out

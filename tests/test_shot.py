@@ -125,20 +125,33 @@ def _oracle_cv2(oracle):
     return cv2
 
 
-@pytest.mark.skipif(not refhost.have_reference(), reason="/root/reference is not present (GPU box)")
+def _reference_shot(height):
+    """pyannote/video/structure/shot.py's Shot on the cut clip (the oracle behind OpenCV's names): what the test below compares with,
+    recorded in tests/golden/reference_pins.json.gz by tests/golden/make_reference_pins.py"""
+    from oracle import oracle
+    from pyannote_video_amd._core import Segment
+    clip = _Clip(_cut_clip())
+    with refhost.reference_shot_module(_oracle_cv2(oracle), Segment) as ref:
+        shot = ref.Shot(clip, height=height, context=0.4, threshold=1.0)
+        return {"pairs": [[float(t), float(d)] for t, d in shot.iter_dfd()], "segments": [[float(s.start), float(s.end)] for s in shot],
+                "kernel_size": int(shot._kernel_size), "resize": [int(v) for v in shot._resize]}
+
+
+def record():
+    return {"shot": {str(h): _reference_shot(h) for h in (50, 100)}}
+
+
 @pytest.mark.parametrize("height", [50, 100])                     # the reference's default (one level) and a two-level size
 def test_reference_shot_class_verbatim_equals_product_host_logic(height):
     from oracle import oracle
     from pyannote_video_amd import structure
-    from pyannote_video_amd._core import Segment
     frames = _cut_clip()
     clip = _Clip(frames)
-    with refhost.reference_shot_module(_oracle_cv2(oracle), Segment) as ref:
-        shot = ref.Shot(clip, height=height, context=0.4, threshold=1.0)
-        ref_pairs = list(shot.iter_dfd())
-        ref_segments = [(s.start, s.end) for s in shot]
-        ksize = shot._kernel_size
-        assert shot._resize == (height, int(160 * height / 120))
+    rec = refhost.recorded("shot")[str(height)]
+    ref_pairs = [tuple(p) for p in rec["pairs"]]
+    ref_segments = [tuple(s) for s in rec["segments"]]
+    ksize = rec["kernel_size"]
+    assert tuple(rec["resize"]) == (height, int(160 * height / 120))
     # the oracle's displaced frame difference == what the reference's per-pixel Python loop computes from the same flow
     ow, oh = height, int(160 * height / 120)
     small = [oracle.shot_convert(f, ow, oh) for f in frames]

@@ -9,12 +9,12 @@ for w in "$@"; do
   case "$w" in
     tests) t tests 1200 python -m pytest tests -q -m gpu --durations=8 -p no:cacheprovider ;;
     smoke) t smoke 200 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" ;;
-    c2) t bench_c2 500 python bench.py ;;
-    c2q) t bench_c2q 300 python bench.py --cpu-frames 0 --no-host-ingest --no-dropin --steps 3 ;;
-    c5) t bench_c5 700 python bench.py --config c5 ;;
-    c4) t bench_c4 700 python bench.py --config c4 ;;
-    c3s) t bench_c3s 400 python bench.py --config c3 --frames 3000 --steps 1 ;;
-    c3) t bench_c3 600 python bench.py --config c3 --steps 1 ;;
+    c2) t bench_c2 500 python bench.py --full ;;
+    c2q) t bench_c2q 300 python bench.py --full --cpu-frames 0 --no-host-ingest --no-dropin --steps 3 ;;
+    c5) t bench_c5 700 python bench.py --full --config c5 ;;
+    c4) t bench_c4 700 python bench.py --full --config c4 ;;
+    c3s) t bench_c3s 400 python bench.py --full --config c3 --frames 3000 --steps 1 ;;
+    c3) t bench_c3 600 python bench.py --full --config c3 --steps 1 ;;
     *) t custom_$(echo "$w" | tr -c 'a-zA-Z0-9' '_' | cut -c1-40) 900 bash -c "$w" ;;
   esac
 done
