@@ -317,6 +317,22 @@ int32_t pvf_debug_tracker_state(pvf_handle ctx, pvf_handle trk, double* F, doubl
 int32_t pvf_shot_dfd(pvf_handle ctx, const pvf_handle* frames, int32_t n, int32_t width, int32_t height, const float* tables,
                      double* dfd, uint8_t* gray_out, float* flow_out);
 
+/* ---- shot threading (ORB.md) ------------------------------------------------------------------------------------
+ * ref: pyannote/video/structure/thread.py:139-150 (_compute_orb: cv2.resize of the RGB frame to `width` x `height`, RGB -> gray,
+ *      cv2.ORB_create().detectAndCompute with OpenCV 3.x defaults: 500 features, 1.2, 8 levels, edge 31, FAST 20, Harris, patch 31).
+ *      For every frame: counts[i] keypoints, rows [i][cap][6] floats (x, y, level, FAST score, Harris response, angle in degrees;
+ *      x and y in pixels of the keypoint's level) ordered by level, then y, then x, and descriptors [i][cap][32].  keypoints and
+ *      descriptors may be NULL.  A frame with more than `cap` keypoints (retainBest keeps every point tied with the last one) is an
+ *      error.  The descriptors stay on the device for pvf_orb_match_counts until the next call on this context. */
+int32_t pvf_orb_extract(pvf_handle ctx, const pvf_handle* frames, int32_t n, int32_t width, int32_t height, int32_t cap,
+                        int32_t* counts, float* keypoints, uint8_t* descriptors);
+/* ref: thread.py:152-170 (_match: FlannBasedMatcher LSH knnMatch(k = 2), ratio 0.7) with an EXACT 2-nearest-neighbour search:
+ *      counts[p] = the rows of set pairs[2p] whose best and second-best Hamming distances d1 <= d2 to the rows of set pairs[2p + 1]
+ *      satisfy 10 d1 < 7 d2; 0 when either set has fewer than 2 rows.  descriptors ([n_sets][cap][32], rows[n_sets] of them used) ==
+ *      NULL: the sets of the last pvf_orb_extract on this context (rows, n_sets and cap ignored). */
+int32_t pvf_orb_match_counts(pvf_handle ctx, const uint8_t* descriptors, const int32_t* rows, int32_t n_sets, int32_t cap,
+                             const int32_t* pairs, int64_t n_pairs, int32_t* counts);
+
 #ifdef __cplusplus
 }
 #endif

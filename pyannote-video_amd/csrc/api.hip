@@ -396,6 +396,28 @@ extern "C" int32_t pvf_shot_dfd(pvf_handle h, const pvf_handle* frames, int32_t 
     API_END
 }
 
+// ---- shot threading (orb.hip) ------------------------------------------------------------------------------------------------
+extern "C" int32_t pvf_orb_extract(pvf_handle h, const pvf_handle* frames, int32_t n, int32_t width, int32_t height, int32_t cap,
+                                   int32_t* counts, float* keypoints, uint8_t* descriptors)
+{
+    API_BEGIN
+    ENTER(c, h);
+    PVF_REQUIRE(n >= 1 && frames, "orb: frames");
+    std::vector<Frame> f(n);
+    for (int i = 0; i < n; ++i) f[i] = c->frame(frames[i]);
+    orb_extract(c, f, width, height, cap, counts, keypoints, descriptors);
+    API_END
+}
+
+extern "C" int32_t pvf_orb_match_counts(pvf_handle h, const uint8_t* descriptors, const int32_t* rows, int32_t n_sets, int32_t cap,
+                                        const int32_t* pairs, int64_t n_pairs, int32_t* counts)
+{
+    API_BEGIN
+    ENTER(c, h);
+    orb_match_counts(c, descriptors, rows, n_sets, cap, pairs, n_pairs, counts);
+    API_END
+}
+
 // ---- S3 (host) --------------------------------------------------------------------------------------
 static double darea(double l, double t, double r, double b) { return (l > r || t > b) ? 0.0 : (r - l) * (b - t); }
 

@@ -271,6 +271,10 @@ struct Ctx {
     const void* feat_ring_owner = nullptr;    // plan whose zero padding ring s_feat currently holds
     uint8_t* d_orient_lut = nullptr; // 511x511 orientation bins (fhog.hip)
     uint8_t* d_wrap_lut = nullptr;       // the same, indexed by the differences mod 512 (2^18 bytes): orientation_lut_wrapped()
+    // shot threading (orb.hip): the keypoints / descriptors of the last pvf_orb_extract ([n][cap] rows + counts), what
+    // pvf_orb_match_counts reads when it is given no descriptors; and the matcher's own pairs / counts / uploaded sets
+    DevBuf s_orb_set, s_orb_work;
+    int orb_n = 0, orb_cap = 0;
 
     // a copy of the frame record (the table may be re-hashed by another thread as soon as the lock is gone)
     Frame frame(uint64_t id)
@@ -383,6 +387,10 @@ void dsst_clone_many(Ctx* c, const std::vector<Tracker*>& src, const std::vector
 double* tracker_state_alloc(Ctx* c);
 // shot boundary detection (shot.hip)
 void shot_dfd(Ctx* c, const std::vector<Frame>& frames, int ow, int oh, const float* tables22, double* dfd, uint8_t* gray_out, float* flow_out);
+// orb.hip: ORB of the shot threading and its Hamming ratio-test matcher
+std::vector<int> orb_level_quota();
+void orb_extract(Ctx* c, const std::vector<Frame>& frames, int ow, int oh, int cap, int32_t* counts, float* kp_out, uint8_t* desc_out);
+void orb_match_counts(Ctx* c, const uint8_t* desc, const int32_t* nrows, int n_sets, int cap, const int32_t* pairs, int64_t n_pairs, int32_t* out);
 void dsst_update_many(Ctx* c, const std::vector<Tracker*>& t, const std::vector<Frame>& f, double* psr, double* boxes_out, int mode = 0);
 // association (assoc.cpp part of api)
 void overlap_matrix_host(const double* a, int na, const double* b, int nb, double ratio, double* out);

@@ -105,6 +105,8 @@ _SIGS = {
     "pvf_debug_extract_chip": (C.c_int32, [H, H, P, C.c_double, C.c_double, C.c_int32, C.c_int32, P]),
     "pvf_debug_tracker_state": (C.c_int32, [H, H, P, P, P]),
     "pvf_shot_dfd": (C.c_int32, [H, P, C.c_int32, C.c_int32, C.c_int32, P, P, P, P]),
+    "pvf_orb_extract": (C.c_int32, [H, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P, P, P]),
+    "pvf_orb_match_counts": (C.c_int32, [H, P, P, C.c_int32, C.c_int32, P, C.c_int64, P]),
 }
 EXPORTS = sorted(_SIGS)
 

@@ -4,6 +4,8 @@
     python -m pyannote_video_amd extract [options] <video> <tracking> <landmark_model> <embedding_model> <landmarks> <embeddings>
     python -m pyannote_video_amd cluster [options] <embeddings> <labels>
     python -m pyannote_video_amd process [options] <video> <shot.json> <landmark_model> <embedding_model> <tracking> <landmarks> <embeddings>
+    python -m pyannote_video_amd shot    [options] <video> <output.json>
+    python -m pyannote_video_amd thread  [--min-match 20] [--lookahead 24] <video> <shot.json> <output.json>
 
 `track` and `extract` take the reference's arguments and options and write byte-compatible files (track.txt, landmarks.txt,
 embedding.txt: formats.py).  `cluster` is the verb BASELINE.json's north_star names; the reference offers clustering through the API
@@ -57,6 +59,16 @@ class NpyVideo(object):
     def __iter__(self):
         for i in range(len(self._frames)):
             yield i / self.frame_rate, np.ascontiguousarray(self._frames[i])
+
+    def frame(self, i):
+        return np.ascontiguousarray(self._frames[i])
+
+    def __call__(self, t):
+        """the frame at time t: index int(fps * t + 1e-5), as the reference's Video reads it (video.py:466-486)"""
+        i = int(self.frame_rate * t + 0.00001)
+        if not 0 <= i < len(self._frames):
+            raise IOError("no frame at t = %.3f" % t)
+        return self.frame(i)
 
 
 def open_video(spec, frame_rate):
@@ -286,6 +298,16 @@ def shot(video, output, height=50, window=2.0, threshold=1.0, ctx=None):
     return segments
 
 
+def thread(video, shot, output, min_match=20, lookahead=24, ctx=None):
+    """Shot threading (scripts/pyannote-structure.py:72-80): reads what `shot` writes, writes a pyannote.core.json Annotation"""
+    from .structure import Thread, Segment
+    shots = [Segment(s.start, s.end) for s in (load_shots(shot) if isinstance(shot, str) else shot)]
+    threads = Thread(video, shot=shots, lookahead=lookahead, min_match=min_match, ctx=ctx)()
+    with open(output, 'w') as fp:
+        json.dump(threads.for_json(), fp)
+    return threads
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="pyannote-face", description="face tracking => feature extraction => face clustering (MI355X)")
     ap.add_argument("--fps", type=float, default=25.0, help="frame rate of a .npy / synthetic video")
@@ -319,6 +341,10 @@ def main(argv=None):
                    "64 and more bring OpenCV's coarser levels)")
     s.add_argument("--window", type=float, default=2.0)
     s.add_argument("--threshold", type=float, default=1.0)
+    th = sub.add_parser("thread", help="shot threading (pyannote-structure.py thread)")
+    th.add_argument("video"); th.add_argument("shot"); th.add_argument("output")
+    th.add_argument("--min-match", type=int, default=20)
+    th.add_argument("--lookahead", type=int, default=24)
     c = sub.add_parser("cluster")
     c.add_argument("embeddings"); c.add_argument("labels")
     c.add_argument("--threshold", type=float, default=0.6)
@@ -341,6 +367,8 @@ def main(argv=None):
                 track_min_confidence=a.min_confidence, track_max_gap=a.max_gap, threshold=a.threshold, ctx=ctx)
     elif a.verb == "shot":
         shot(open_video(a.video, a.fps), a.output, height=a.height, window=a.window, threshold=a.threshold, ctx=ctx)
+    elif a.verb == "thread":
+        thread(open_video(a.video, a.fps), a.shot, a.output, min_match=a.min_match, lookahead=a.lookahead, ctx=ctx)
     elif a.verb == "extract":
         extract(open_video(a.video, a.fps), a.landmark_model, a.embedding_model, a.tracking, a.landmarks, a.embeddings, ctx=ctx)
     else:

@@ -540,6 +540,37 @@ class Context(object):
             out += (flow,)
         return out if len(out) > 1 else dfd
 
+    # ---- shot threading (csrc/orb.hip)
+    def orb_extract(self, frames, width, height, cap=1024):
+        """ORB of the reference's shot threading (structure/thread.py:139-150) on every frame: the frame resized to width x height,
+        gray, cv2.ORB_create() defaults.  Returns (counts int32 [n], keypoints float32 [n, cap, 6] = (x, y, level, FAST score, Harris
+        response, angle) in level / y / x order, descriptors uint8 [n, cap, 32]); rows past counts[i] are unused.  The descriptors
+        stay on the device for orb_match_counts(pairs)."""
+        n = len(frames)
+        counts = np.zeros(n, np.int32)
+        kp = np.zeros((n, cap, 6), np.float32)
+        desc = np.zeros((n, cap, 32), np.uint8)
+        with self._staging():
+            check(self._l.pvf_orb_extract(self._h, ptr(self._handles(frames)), n, int(width), int(height), int(cap), ptr(counts),
+                                          ptr(kp), ptr(desc)))
+        return counts, kp, desc
+
+    def orb_match_counts(self, pairs, descriptors=None, rows=None):
+        """counts[p] = rows of set pairs[p][0] whose two nearest rows of set pairs[p][1] (Hamming) pass the ratio test 10 d1 < 7 d2
+        (thread.py:152-170 with an exact 2-NN); 0 when either set has fewer than 2 rows.  descriptors uint8 [n_sets, cap, 32] with
+        rows[n_sets] used rows each; None: the sets of the last orb_extract on this context."""
+        pr = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
+        out = np.zeros(len(pr), np.int32)
+        if descriptors is None:
+            check(self._l.pvf_orb_match_counts(self._h, None, None, 0, 0, ptr(pr), len(pr), ptr(out)))
+        else:
+            d = np.ascontiguousarray(descriptors, np.uint8)
+            if d.ndim != 3 or d.shape[2] != 32:
+                raise ValueError("descriptors: uint8 [n_sets, cap, 32]")
+            r = np.ascontiguousarray(rows, np.int32)
+            check(self._l.pvf_orb_match_counts(self._h, ptr(d), ptr(r), d.shape[0], d.shape[1], ptr(pr), len(pr), ptr(out)))
+        return out
+
     # ---- S5
     def pair_mean_dist(self, X, row_start, metric=0):
         """T x T matrix of mean pair distances between the rows of two tracks; metric 0 = Euclidean (reference), 1 = cosine"""
