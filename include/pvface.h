@@ -323,7 +323,10 @@ int32_t pvf_shot_dfd(pvf_handle ctx, const pvf_handle* frames, int32_t n, int32_
  *      For every frame: counts[i] keypoints, rows [i][cap][6] floats (x, y, level, FAST score, Harris response, angle in degrees;
  *      x and y in pixels of the keypoint's level) ordered by level, then y, then x, and descriptors [i][cap][32].  keypoints and
  *      descriptors may be NULL.  A frame with more than `cap` keypoints (retainBest keeps every point tied with the last one) is an
- *      error.  The descriptors stay on the device for pvf_orb_match_counts until the next call on this context. */
+ *      error; cap is at most 65536.  On that error counts (if not NULL) is still written: counts[i] = -(keypoints of frame i) for
+ *      every frame that does not fit, so the largest -counts[i] is the cap a second call needs; keypoints and descriptors are not
+ *      written.  The descriptors stay on the device for pvf_orb_match_counts until the next call on this context; a call that
+ *      fails leaves none. */
 int32_t pvf_orb_extract(pvf_handle ctx, const pvf_handle* frames, int32_t n, int32_t width, int32_t height, int32_t cap,
                         int32_t* counts, float* keypoints, uint8_t* descriptors);
 /* ref: thread.py:152-170 (_match: FlannBasedMatcher LSH knnMatch(k = 2), ratio 0.7) with an EXACT 2-nearest-neighbour search:

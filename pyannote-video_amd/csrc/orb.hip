@@ -319,7 +319,8 @@ __global__ void __launch_bounds__(256) orb_level_k(const uint8_t* __restrict__ p
     }
 }
 
-// per frame: its levels one after the other into rows [frame * cap, ...) of the resident set; counts[frame] = -1 when they do not fit
+// per frame: its levels one after the other into rows [frame * cap, ...) of the resident set; counts[frame] = -(rows the frame needs)
+// when they do not fit
 __global__ void __launch_bounds__(256) orb_pack_k(const Kp* __restrict__ slot_kp, const uint8_t* __restrict__ slot_desc,
                                                   const int* __restrict__ slot_n, int nlev, int cap, int first, Kp* __restrict__ kp_out,
                                                   uint8_t* __restrict__ desc_out, int* __restrict__ counts)
@@ -335,7 +336,7 @@ __global__ void __launch_bounds__(256) orb_pack_k(const Kp* __restrict__ slot_kp
     }
     over |= start[kLevels] > cap;
     const size_t row0 = (size_t)(first + f) * cap;
-    if (threadIdx.x == 0) counts[first + f] = over ? -1 : start[kLevels];
+    if (threadIdx.x == 0) counts[first + f] = over ? -start[kLevels] : start[kLevels];
     if (over) return;
     for (int i = threadIdx.x; i < start[kLevels]; i += 256) {
         int l = 0;
@@ -450,6 +451,7 @@ std::vector<int> orb_level_quota()
 void orb_extract(Ctx* c, const std::vector<Frame>& frames, int ow, int oh, int cap, int32_t* counts, float* kp_out, uint8_t* desc_out)
 {
     const int n = (int)frames.size();
+    c->orb_n = 0;                                             // a refused or failed call leaves no resident set behind
     PVF_REQUIRE(n >= 1 && ow >= 1 && oh >= 1 && ow <= kMaxSide && oh <= kMaxSide, "orb: at least one frame and a small image of at most 4095 x 4095");
     PVF_REQUIRE(cap >= 1 && cap <= 65536, "orb: cap (keypoints per frame) in [1, 65536]");
     const int ih = frames[0].h, iw = frames[0].w;
@@ -528,13 +530,16 @@ void orb_extract(Ctx* c, const std::vector<Frame>& frames, int ow, int oh, int c
     std::vector<int32_t> cnt(n);
     HIP_CHECK(hipMemcpyAsync(cnt.data(), d_cnt, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_CHECK(hipStreamSynchronize(c->stream));
+    if (counts) memcpy(counts, cnt.data(), (size_t)n * 4);            // (also on the error below: -needed marks the frames that do not fit)
+    int first_over = -1, need = 0;
     for (int i = 0; i < n; ++i)
-        if (cnt[i] < 0) {
-            char b[160];
-            snprintf(b, sizeof b, "orb: frame %d has more keypoints (ties of retainBest included) than cap = %d: call again with a larger cap", i, cap);
-            throw PvfError(b);
-        }
-    if (counts) memcpy(counts, cnt.data(), (size_t)n * 4);
+        if (cnt[i] < 0) { if (first_over < 0) first_over = i; need = std::max(need, -cnt[i]); }
+    if (first_over >= 0) {
+        char b[256];
+        snprintf(b, sizeof b, "orb: frame %d has %d keypoints (ties of retainBest included), more than cap = %d; the largest frame needs cap >= %d: "
+                 "call again with a larger cap", first_over, -cnt[first_over], cap, need);
+        throw PvfError(b);
+    }
     if (kp_out) HIP_CHECK(hipMemcpy(kp_out, d_kp, (size_t)n * cap * sizeof(Kp), hipMemcpyDeviceToHost));
     if (desc_out) HIP_CHECK(hipMemcpy(desc_out, d_desc, (size_t)n * cap * 32, hipMemcpyDeviceToHost));
     c->orb_n = n;

@@ -15,6 +15,14 @@ class PvfError(RuntimeError):
     pass
 
 
+class OrbCapError(PvfError):
+    """pvf_orb_extract: a frame has more keypoints than the cap; `needed` is the cap that fits every frame of the call"""
+
+    def __init__(self, message, needed):
+        PvfError.__init__(self, message)
+        self.needed = int(needed)
+
+
 class Rect(C.Structure):
     _fields_ = [("left", C.c_int32), ("top", C.c_int32), ("right", C.c_int32), ("bottom", C.c_int32)]
 

@@ -541,18 +541,40 @@ class Context(object):
         return out if len(out) > 1 else dfd
 
     # ---- shot threading (csrc/orb.hip)
-    def orb_extract(self, frames, width, height, cap=1024):
+    ORB_CAP, ORB_CAP_MAX = 1024, 65536     # keypoint rows per frame: the first try of orb_extract, the library's limit
+
+    def orb_extract(self, frames, width, height, cap=None):
         """ORB of the reference's shot threading (structure/thread.py:139-150) on every frame: the frame resized to width x height,
         gray, cv2.ORB_create() defaults.  Returns (counts int32 [n], keypoints float32 [n, cap, 6] = (x, y, level, FAST score, Harris
         response, angle) in level / y / x order, descriptors uint8 [n, cap, 32]); rows past counts[i] are unused.  The descriptors
-        stay on the device for orb_match_counts(pairs)."""
+        stay on the device for orb_match_counts(pairs).
+        cap None: ORB_CAP rows, and when a frame has more keypoints (retainBest keeps every point tied with the last one, so a level
+        can exceed its quota) the call is repeated once with the cap the largest frame needs.  A given cap is strict: a frame with
+        more keypoints raises OrbCapError; nothing is truncated."""
+        if cap is not None:
+            return self._orb_extract(frames, width, height, int(cap))
+        try:
+            return self._orb_extract(frames, width, height, self.ORB_CAP)
+        except _lib.OrbCapError as e:
+            if e.needed > self.ORB_CAP_MAX:
+                raise _lib.OrbCapError("orb: a frame has %d keypoints (ties of retainBest included), more than the %d rows per frame the "
+                                       "library can return" % (e.needed, self.ORB_CAP_MAX), e.needed)
+            return self._orb_extract(frames, width, height, e.needed)
+
+    def _orb_extract(self, frames, width, height, cap):
+        """one pvf_orb_extract call; OrbCapError (with the cap every frame fits in) when a frame has more than `cap` keypoints"""
         n = len(frames)
         counts = np.zeros(n, np.int32)
         kp = np.zeros((n, cap, 6), np.float32)
         desc = np.zeros((n, cap, 32), np.uint8)
         with self._staging():
-            check(self._l.pvf_orb_extract(self._h, ptr(self._handles(frames)), n, int(width), int(height), int(cap), ptr(counts),
-                                          ptr(kp), ptr(desc)))
+            rc = self._l.pvf_orb_extract(self._h, ptr(self._handles(frames)), n, int(width), int(height), int(cap), ptr(counts), ptr(kp),
+                                         ptr(desc))
+        if rc != 0:
+            msg = self._l.pvf_last_error().decode("utf-8", "replace")
+            if n and counts.min() < 0:                    # -needed for the frames that did not fit (include/pvface.h)
+                raise _lib.OrbCapError(msg, -int(counts.min()))
+            raise _lib.PvfError(msg)
         return counts, kp, desc
 
     def orb_match_counts(self, pairs, descriptors=None, rows=None):

@@ -245,11 +245,11 @@ class Thread(object):
     min_match : int, optional   shots are linked when MORE than this many descriptors pass the ratio test.  Defaults to 20.
     lookahead : int, optional   each shot is compared with the next `lookahead` shots.  Defaults to 5 (the CLI passes 24).
     ctx : runtime.Context
-    cap : keypoints a frame may keep (500 plus the ties retainBest keeps)
+    cap : keypoints a frame may keep (500 plus the ties retainBest keeps); None: as many as the frames have (Context.orb_extract)
     chunk : frames extracted per call
     """
 
-    def __init__(self, video, shot=None, height=200, min_match=20, lookahead=5, verbose=False, ctx=None, cap=1024, chunk=512):
+    def __init__(self, video, shot=None, height=200, min_match=20, lookahead=5, verbose=False, ctx=None, cap=None, chunk=512):
         self.video = video
         self.height = height
         w, h = self.video._size
@@ -264,7 +264,7 @@ class Thread(object):
         self.shot = shot
         self.verbose = verbose
         self.min_match = min_match
-        self.cap, self.chunk = int(cap), int(chunk)
+        self.cap, self.chunk = None if cap is None else int(cap), int(chunk)
 
     def _frame_index(self, t):
         """video(t) reads frame int(fps * t + 1e-5) (video.py:486, truncation toward zero); None where there is no such frame"""
@@ -302,12 +302,14 @@ class Thread(object):
             got = self.ctx.orb_match_counts(set_pairs)
         else:
             rows = np.zeros(len(needed), np.int32)
-            desc = np.zeros((len(needed), self.cap, 32), np.uint8)
+            desc = np.zeros((len(needed), 0, 32), np.uint8)
             for j0 in range(0, len(needed), self.chunk):
                 part = needed[j0:j0 + self.chunk]
                 n, _, d = self.ctx.orb_extract([self._read(f) for f in part], ow, oh, self.cap)
+                if d.shape[1] > desc.shape[1]:          # the first chunk, or one whose frames needed a larger cap: widen every set
+                    desc = np.pad(desc, ((0, 0), (0, d.shape[1] - desc.shape[1]), (0, 0)))
                 rows[j0:j0 + len(part)] = n
-                desc[j0:j0 + len(part)] = d
+                desc[j0:j0 + len(part), :d.shape[1]] = d
             got = self.ctx.orb_match_counts(set_pairs, desc, rows)
         counts[valid] = got
         return shots, pairs, counts

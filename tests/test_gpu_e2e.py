@@ -87,7 +87,7 @@ def test_device_resize_equals_cv2_restatement(ctx, oracle, small_video):
     """pvf_frame_resize (OpenCV's 8-bit bilinear on the device, reference video.py:402-403) == the oracle's restatement, byte for byte"""
     f = small_video.frame(0)
     dev = ctx.upload(f)
-    for (w, h) in [(320, 180), (333, 187), (640, 360), (500, 300), (97, 55)]:
+    for (w, h) in [(320, 180), (333, 187), (640, 360), (500, 300), (97, 55), (800, 450), (1280, 720), (641, 359), (700, 300)]:
         got = ctx.pyramid_level(ctx.resize(dev, w, h), 0, 0)          # level 0 without upsampling = the frame's bytes
         assert got.shape == (h, w, 3) and np.array_equal(got, oracle.cv_resize(f, w, h)), (w, h)
 

@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+import orb_check
 import orb_ref
 import thread_clip
 
@@ -28,17 +29,7 @@ def _textured(h, w, seed):
 
 
 def _check_frames(gctx, frames):
-    ow, oh = orb_ref.thread_size(frames[0].shape[1], frames[0].shape[0])
-    counts, kp, desc = gctx.orb_extract(frames, ow, oh)
-    for i, f in enumerate(frames):
-        rk, rd = orb_ref.orb_frame(f)
-        n = counts[i]
-        assert n == len(rk), (i, n, len(rk))
-        np.testing.assert_array_equal(kp[i, :n, :4], rk[:, :4].astype(np.float32))
-        np.testing.assert_array_equal(kp[i, :n, 4], rk[:, 4].astype(np.float32))       # Harris response, bit for bit
-        np.testing.assert_array_equal(kp[i, :n, 5], rk[:, 5].astype(np.float32))       # angle, bit for bit
-        np.testing.assert_array_equal(desc[i, :n], rd)
-    return counts
+    return orb_check.check_frames(gctx, frames)[0]        # count, keypoint rows and descriptors against orb_ref, bit for bit
 
 
 @pytest.mark.parametrize("h,w", [(720, 1280), (1080, 1920), (2160, 3840)])

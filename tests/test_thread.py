@@ -193,3 +193,127 @@ def test_thread_frame_index_rule():
     assert th._frame_index(0.0) == 0 and th._frame_index(3 / fps) == 3 and th._frame_index(4 / fps) is None
     assert th._frame_index(-0.5 / fps) == 0 and th._frame_index(-1.5 / fps) is None
     assert th._frame_index(0.12) == 3                       # 25 * 0.12 = 2.9999999999999996: + 1e-5 then truncation
+
+
+# ---- the resize both device copies of INTER_LINEAR implement (ingest.hip's pvf_frame_resize, orb.hip's level 0): orb_ref's
+# restatement == the oracle's, byte for byte, over the GPU tests' geometry table (upscales, odd sizes, one axis up and one down)
+RESIZE_CASES = [((1440, 1080), (200, 266)), ((1080, 1920), (200, 112)), ((160, 120), (200, 266)), ((200, 200), (200, 200)),
+                ((853, 479), (200, 356)), ((3000, 500), (200, 1200)), ((4095, 200), (200, 4095)), ((63, 200), (200, 63)),
+                ((1920, 1080), (300, 533)), ((640, 360), (800, 450)), ((640, 360), (1280, 720)), ((640, 360), (641, 359)),
+                ((640, 360), (700, 300)), ((97, 55), (640, 360)), ((1, 1), (5, 3)), ((2, 3), (7, 9)), ((3, 2), (200, 100))]
+
+
+@pytest.mark.parametrize("src,dst", RESIZE_CASES, ids=["%dx%d-%dx%d" % (s + d) for s, d in RESIZE_CASES])
+def test_resize_restatements_agree(oracle, src, dst):
+    img = np.random.default_rng(src[0] * 7 + dst[1]).integers(0, 256, (src[1], src[0], 3), dtype=np.uint8)
+    got = orb_ref.resize_linear_rgb(img, *dst)
+    assert got.shape == (dst[1], dst[0], 3)
+    np.testing.assert_array_equal(got, oracle.cv_resize(img, *dst))
+
+
+# ---- structure.Thread over a CPU stand-in of the library: Context.orb_extract's cap handling and Thread's chunks
+def _dot_grid(spacing, size=200):
+    g = np.full((size, size, 3), 40, np.uint8)
+    g[::spacing, ::spacing] = 220
+    return g
+
+
+class _OrbStandIn(object):
+    """stands in for libpvface's two ORB entry points on the CPU (orb_ref): Context._orb_extract raises as pvf_orb_extract does when a
+    frame has more keypoints than the cap (OrbCapError carrying the cap that fits), and orb_match_counts matches the resident sets of
+    the last successful call or the host descriptors it is given.  Context's own orb_extract runs on top of it."""
+
+    def __new__(cls):
+        from pyannote_video_amd.runtime import Context
+        stand_in = type("OrbStandInContext", (Context,), {k: v for k, v in vars(cls).items() if k.startswith(("_orb", "orb"))})
+        obj = Context.__new__(stand_in)
+        obj._h, obj.caps, obj.matched, obj._resident, obj._memo = None, [], [], None, {}
+        return obj
+
+    def _orb_extract(self, frames, width, height, cap):
+        from pyannote_video_amd._lib import OrbCapError
+        self.caps.append(cap)
+        self._resident = None
+        refs = []
+        for f in frames:
+            key = (f.tobytes(), width, height)
+            if key not in self._memo:
+                self._memo[key] = orb_ref.orb_gray(orb_ref.gray(orb_ref.resize_linear_rgb(f, width, height)))
+            refs.append(self._memo[key])
+        counts = np.array([len(k) for k, _ in refs], np.int32)
+        if counts.max() > cap:
+            raise OrbCapError("orb: frame %d has %d keypoints, more than cap = %d" % (counts.argmax(), counts.max(), cap), counts.max())
+        kp = np.zeros((len(frames), cap, 6), np.float32)
+        desc = np.zeros((len(frames), cap, 32), np.uint8)
+        for i, (k, d) in enumerate(refs):
+            kp[i, :len(k)] = k
+            desc[i, :len(d)] = d
+        self._resident = (desc, counts)
+        return counts, kp, desc
+
+    def orb_match_counts(self, pairs, descriptors=None, rows=None):
+        if descriptors is None:
+            descriptors, rows = self._resident
+        self.matched.append((descriptors, rows))
+        return np.array([orb_ref.match_count(descriptors[a, :rows[a]], descriptors[b, :rows[b]]) for a, b in pairs], np.int32)
+
+
+def _grid_clip(fps=25.0, per=12):
+    """200 x 200 shots A B G A C, G a dot grid: its frames need more than the default 1024 rows"""
+    tex, _, _ = thread_clip.make_clip(width=200, height=200, frames_per_shot=per, setups="ABAC", frame_rate=fps)
+    frames = np.concatenate([tex[:2 * per], np.stack([_dot_grid(4)] * per), tex[2 * per:]])
+    return frames, [(i * per / fps, (i + 1) * per / fps) for i in range(5)], fps
+
+
+def test_thread_chunks_with_different_caps():
+    from pyannote_video_amd import structure
+    frames, shots, fps = _grid_clip()
+    video = thread_clip.ClipVideo(frames, fps)
+    segs = [structure.Segment(a, b) for a, b in shots]
+    grid_rows = len(orb_ref.orb_gray(orb_ref.gray(_dot_grid(4)))[0])
+    assert grid_rows > 1024
+    one = _OrbStandIn()
+    _, pairs, counts = structure.Thread(video, shot=segs, lookahead=24, ctx=one).match_counts()
+    assert one.caps == [1024, grid_rows]                                  # the default cap, then once more with the cap that fits
+    # needed frames 2 14 | 22 26 | 34 38 | 46 58 in chunks of 2, the grid's at 26 and 34: caps 1024, 1024 then more, 1024 then more, 1024
+    chunked = _OrbStandIn()
+    chunked._memo = one._memo
+    _, _, got = structure.Thread(video, shot=segs, lookahead=24, ctx=chunked, chunk=2).match_counts()
+    assert chunked.caps == [1024, 1024, grid_rows, 1024, grid_rows, 1024]
+    np.testing.assert_array_equal(got, counts)
+    desc, rows = chunked.matched[-1]
+    assert desc.shape[1] == grid_rows                                      # every set padded to the widest chunk
+    needed = [2, 14, 22, 26, 34, 38, 46, 58]
+    for j, f in enumerate(needed):
+        _, d = one._memo[(np.ascontiguousarray(frames[f]).tobytes(), 200, 200)]
+        assert rows[j] == len(d)
+        np.testing.assert_array_equal(desc[j, :rows[j]], d)
+        assert not desc[j, rows[j]:].any()
+    # both equal the restatement of thread.py's pairs
+    collar = 10. / fps
+    ref = [orb_ref.match_count(one._memo[(np.ascontiguousarray(frames[int(fps * (shots[i][1] - collar) + 1e-5)]).tobytes(), 200, 200)][1],
+                               one._memo[(np.ascontiguousarray(frames[int(fps * (shots[k][0] + collar) + 1e-5)]).tobytes(), 200, 200)][1])
+           for i, k in pairs]
+    np.testing.assert_array_equal(counts, ref)
+
+
+def test_orb_cap_explicit_is_strict_and_limit_is_clear():
+    from pyannote_video_amd import structure
+    from pyannote_video_amd._lib import OrbCapError
+    frames, shots, fps = _grid_clip()
+    video = thread_clip.ClipVideo(frames, fps)
+    segs = [structure.Segment(a, b) for a, b in shots]
+    ctx = _OrbStandIn()
+    with pytest.raises(OrbCapError, match="more than cap = 1024"):
+        structure.Thread(video, shot=segs, lookahead=24, ctx=ctx, cap=1024).match_counts()
+    assert ctx.caps == [1024]                                              # a given cap: no second call
+    grid = _dot_grid(4)
+    n = ctx.orb_extract([grid], 200, 200)[0][0]
+    with pytest.raises(OrbCapError) as e:
+        ctx.orb_extract([grid, grid], 200, 200, cap=n - 1)
+    assert e.value.needed == n
+    ctx.ORB_CAP_MAX = n - 1                                                # a frame past the library's limit: one clear error
+    ctx.caps = []
+    with pytest.raises(OrbCapError, match="%d keypoints .* more than the %d rows" % (n, n - 1)):
+        ctx.orb_extract([grid], 200, 200)
+    assert ctx.caps == [1024]
