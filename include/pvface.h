@@ -125,6 +125,17 @@ int32_t pvf_detector_screening(pvf_handle ctx, int32_t on, int32_t list_cap);
  * for every context the process creates. */
 int32_t pvf_detector_screening_stats(pvf_handle ctx, int64_t* batches, int64_t* listed, int64_t* retries, double* bounds, double* pipe_err);
 
+/* the embedder's convolutions on the f16 matrix cores with split operands (on by default; csrc/resnet.hip: conv_split_k).  on = 1:
+ * every convolution outside the 32-channel stage runs as three f16 products of hi / lo halves (scaled by fixed powers of two) with an
+ * fp32 accumulation -- descriptors within the error bound of DESIGN.md section 4, no longer the oracle's chain order; a face whose
+ * activations leave the f16 range is embedded again on the exact kernels.  on = 0: the exact fp32 kernels only.  The environment
+ * variable PVF_EMBEDDER_SPLIT=0 switches the split off for every context the process creates. */
+int32_t pvf_embedder_split(pvf_handle ctx, int32_t on);
+/* faces embedded with the split on, faces of those embedded again on the exact kernels, and pipe_err = what the context measured on
+ * its device before the first split forward: worst |matrix pipe - exact| / sum of magnitudes over an accumulation of 2304 terms (-1
+ * before that; the bound allows 2304 x 2^-22) -- since the context was created */
+int32_t pvf_embedder_split_stats(pvf_handle ctx, int64_t* faces, int64_t* reruns, double* pipe_err);
+
 /* ---- S2 correlation tracker ------------------------------------------------------------------------ */
 /* ref: tracking.py:250  dlib.correlation_tracker() */
 int32_t pvf_tracker_create(pvf_handle ctx, pvf_handle* trk);

@@ -80,6 +80,24 @@ extern "C" int32_t pvf_detector_screening_stats(pvf_handle h, int64_t* batches, 
     API_END
 }
 
+extern "C" int32_t pvf_embedder_split(pvf_handle h, int32_t on)
+{
+    API_BEGIN
+    ENTER(c, h);
+    c->emb_split = on != 0;
+    API_END
+}
+
+extern "C" int32_t pvf_embedder_split_stats(pvf_handle h, int64_t* faces, int64_t* reruns, double* pipe_err)
+{
+    API_BEGIN
+    ENTER(c, h);
+    if (faces) *faces = c->emb_split_faces;
+    if (reruns) *reruns = c->emb_reruns;
+    if (pipe_err) *pipe_err = c->emb_pipe_err;
+    API_END
+}
+
 extern "C" int32_t pvf_detect_batch(pvf_handle h, const pvf_handle* frames, int32_t n_frames, int32_t upsample, double adjust,
                                     pvf_rect_i32* out, float* scores, int32_t* counts, int32_t cap)
 {

@@ -1,6 +1,7 @@
 // ctx.hip -- context, model containers, frames, HIP-event profiling.
 #include "pvf_internal.h"
 #include "detect_ml.h"
+#include <cmath>
 #include <fstream>
 #include <mutex>
 #include <dlfcn.h>
@@ -167,7 +168,10 @@ static void load_embedder(Ctx* c, const char* path)
     const Tensor& blob = need(m, "emb.blob");
     const float* p = blob.f32();
     const float* end = p + blob.numel();
-    for (ConvLayer& L : e.convs) if (L.d_frag) { (void)hipFree(L.d_frag); L.d_frag = nullptr; }
+    for (ConvLayer& L : e.convs) {
+        if (L.d_frag) { (void)hipFree(L.d_frag); L.d_frag = nullptr; }
+        if (L.d_wsplit) { (void)hipFree(L.d_wsplit); L.d_wsplit = nullptr; }
+    }
     e.convs.clear();
     if (e.d_stem) { (void)hipFree(e.d_stem); e.d_stem = nullptr; }     // (fragment-ordered copy of the first layer's weights: rebuilt on the next forward)
     auto add_conv = [&](int cin, int cout, int k, int stride, int pad) {
@@ -188,6 +192,11 @@ static void load_embedder(Ctx* c, const char* path)
                         wt[(size_t)o * Kpad + kk] = p[(((size_t)o * cin + ci) * k + r) * k + s];
                     }
         L.d_w = upload<float>(wt.data(), wt.size());
+        // the split path's weight scale: a power of two that puts the largest |w| in [2^14, 2^15) (a function of the weights only)
+        float wmax = 0.0f;
+        for (float v : wt) wmax = std::max(wmax, std::fabs(v));
+        int ex = 0;
+        if (wmax > 0.0f && std::isfinite(wmax)) { std::frexp(wmax, &ex); L.w_exp = 15 - ex; }     // wmax = f 2^ex, f in [0.5, 1)
         p += nw;
         L.d_bias = upload<float>(p, cout); p += cout;
         L.d_gamma = upload<float>(p, cout); p += cout;
@@ -319,6 +328,7 @@ extern "C" int32_t pvf_ctx_create_prio(int32_t device, int32_t priority_class, p
         HIP_CHECK(hipStreamCreateWithPriority(&c->det_stream, hipStreamNonBlocking, priority_class == 2 ? hi : lo));
     }
     if (const char* e = getenv("PVF_DETECTOR_SCREENING")) c->det_screen = atoi(e) != 0;     // (what pvf_detector_screening sets: 0 = dense scoring only)
+    if (const char* e = getenv("PVF_EMBEDDER_SPLIT")) c->emb_split = atoi(e) != 0;          // (what pvf_embedder_split sets: 0 = exact fp32 kernels only)
     std::lock_guard<std::mutex> lk(g_ctx_mu);
     uint64_t id = g_next_ctx++;
     g_ctxs[id] = std::move(c);

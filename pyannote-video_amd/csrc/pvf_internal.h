@@ -160,6 +160,8 @@ struct ConvLayer {
     float* d_gamma; // [cout]
     float* d_beta;  // [cout]
     float* d_frag = nullptr;   // 32 -> 32 layers: d_w in MFMA fragment order [k-pairs][64 lanes] (resnet.hip: conv_frag_k), made on first use
+    int w_exp = 0;             // split path: the weights are scaled by 2^w_exp (largest |w| in [2^14, 2^15)), set at model load
+    uint32_t* d_wsplit = nullptr;   // split path: f16 hi / lo halves of d_w * 2^w_exp (resnet.hip: conv_wsplit_k), made on first use
 };
 
 struct EmbedModel {
@@ -259,6 +261,11 @@ struct Ctx {
     int64_t screen_batches = 0, screen_listed = 0, screen_retries = 0;
     double screen_pipe_err = -1;              // measured by screen_probe: worst |pipe - exact| / sum of magnitudes over its K = 3200 accumulations (five cases)
     bool screen_pipe_flushes_subnormals = false;      // screen_probe case 4 (the bound carries the term e_sub either way)
+    // the embedder's convolutions on the f16 matrix cores with split operands (resnet.hip: conv_split_k; pvf_embedder_split)
+    bool emb_split = true, emb_probe_done = false;
+    DevBuf s_emb_flags, s_emb_redo;
+    int64_t emb_split_faces = 0, emb_reruns = 0;
+    double emb_pipe_err = -1;                 // measured by embed_probe: worst |pipe - exact| / sum of magnitudes over K = 2304 accumulations
     int n_cu = 256;
     // released frame buffers by size.  A buffer comes back with the event recorded on the compute stream at its release: whoever takes it
     // next orders its first write behind that event (pool_take), so releasing a frame never waits for the kernels that still read it.

@@ -10,6 +10,9 @@
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 // ---------------------------------------------------------------------------------------------------
 // chip alignment geometry (host; a few doubles per face).  [EXT get_face_chip_details + chip_details]
@@ -58,6 +61,9 @@ struct ConvArgs {
     int relu;
     int skip_mode;                     // 0 none, 1 identity [B][OH][OW][Cout], 2 avg-pool 2x2 s2 of x [B][XH][XW][XC]
     const float* skip; int XH, XW, XC, SH, SW;
+    // split path (conv_split_k): the weights as f16 hi / lo halves of (w * 2^w_exp), [Cout][Kpad / 32][32 hi, 32 lo]; activations are
+    // scaled by 2^EMB_A_SCALE_EXP; out_scale = 2^-(w_exp + 8) undoes both; flags[face] = 1 when a scaled input would overflow f16
+    const uint32_t* wsplit; float out_scale; int* flags;
 };
 
 // Implicit-GEMM convolution on v_mfma_f32_32x32x2_f32.  Block tile BM x BN = (64 WM) x (32 WN) output pixels x channels, 4 waves; a wave owns
@@ -291,6 +297,182 @@ __global__ void __launch_bounds__(256) conv_mfma_k(ConvArgs a)
 // profiles/r04_conv_lds_vs_regs.txt -- and a spatial input tile reused across the 9 taps, one fetch per pixel and one barrier per block,
 // round 5 -- profiles/r05_conv_band_experiment.txt: a layer's MFMAs and its unavoidable HBM traffic are of the same size and run one
 // after the other inside a block; the staging of the A operand is not what the matrix pipe waits for.)
+
+// ---------------------------------------------------------------------------------------------------
+// The same convolution on the f16 matrix cores with split operands (the default; pvf_embedder_split).  Every scaled operand is a pair
+// of f16 halves, v = hi + lo + e with hi = f16(v), lo = f16(v - hi) (v - hi is exact in fp32), and a product is three
+// v_mfma_f32_32x32x16_f16 terms, hi.hi + hi.lo + lo.hi, accumulated in fp32 (DESIGN.md section 4 for the bound).  The scales are fixed
+// powers of two: activations x 2^8 (EMB_A_SCALE_EXP, the same for every layer and face), weights x 2^w_exp per layer with the
+// largest |w| in [2^14, 2^15) (from the weights at model load); the epilogue multiplies by 2^-(8 + w_exp), exactly, before the fp32
+// arithmetic of conv_epilogue.  No scale depends on the data, so a face's descriptor never depends on its batch-mates.  A scaled input
+// that f16 cannot hold (|x| >= 65504 / 256) marks its face in a.flags; resnet_forward embeds those faces again on the exact kernels.
+// Tiles and staging are conv_mfma_k's; an LDS row holds a chunk's 32 hi halves (16 dwords), then its 32 lo halves, padded to 36
+// dwords: lane (i, h) of k-step s (k = 16 s + 8 h + j) reads hi at dword 8 s + 4 h and lo 16 dwords behind, one ds_read_b128 each
+// (conflict-free with the 36-dword pitch).  A is split on the way into LDS; B (split once per model, conv_wsplit_k) is copied as is.
+#define EMB_A_SCALE_EXP 8
+#define EMB_F16_LIMIT 65504.0f
+
+// w [cout][Kpad] fp32 -> out [cout][Kpad / 32][32 hi, 32 lo] f16 of w * 2^w_exp
+__global__ void __launch_bounds__(256) conv_wsplit_k(const float* __restrict__ w, int total, int w_exp, _Float16* __restrict__ out)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const float v = ldexpf(w[i], w_exp);
+    const _Float16 hi = (_Float16)v;
+    const _Float16 lo = (_Float16)(v - (float)hi);
+    const int row32 = i >> 5, kk = i & 31;                // (cout, chunk) rows of 32 k
+    out[(size_t)row32 * 64 + kk] = hi;
+    out[(size_t)row32 * 64 + 32 + kk] = lo;
+}
+
+template <int WM, int WN>
+__global__ void __launch_bounds__(256) conv_split_k(ConvArgs a)
+{
+    constexpr int BM = 64 * WM, BN = 32 * WN, KC = 32, PITCH = 36;
+    static_assert(WM * WN == 4, "four waves per block");
+    constexpr int SM_ROWS = (BM + BN > 256) ? BM + BN : 256;
+    __shared__ __attribute__((aligned(16))) float smem[SM_ROWS * PITCH];
+    uint32_t* As = reinterpret_cast<uint32_t*>(smem);
+    uint32_t* Bs = As + BM * PITCH;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave / WN, wn = wave % WN;
+    const long M = (long)a.B * a.OH * a.OW;
+    const long m0 = (long)blockIdx.x * BM;
+    const int n0 = blockIdx.y * BN;
+    f32x16 acc0, acc1;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { acc0[i] = 0.0f; acc1[i] = 0.0f; }
+
+    constexpr int A_F4 = BM * 8 / 256, B_F4 = BN * 8 / 256;
+    constexpr int RSRC_FLAGS = 0x00020000;
+    constexpr int OOB = (int)0x80000000;
+    const int hw = a.OH * a.OW;
+    const int b_first = (int)(m0 / hw);
+    const int rel0 = (int)(m0 - (long)b_first * hw);
+    const float r_hw = 1.0f / (float)hw, r_ow = 1.0f / (float)a.OW;
+    const size_t face = (size_t)a.H * a.W * a.Cin;
+    const size_t in_bytes = (size_t)(a.B - b_first) * face * sizeof(float);
+    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc((void*)(a.in + (size_t)b_first * face), 0,
+                                                                           in_bytes > 0x7ffffff0u ? 0x7ffffff0 : (int)in_bytes, RSRC_FLAGS);
+    int pa_off[A_F4], pa_y[A_F4], pa_x[A_F4];
+#pragma unroll
+    for (int q = 0; q < A_F4; ++q) {
+        const int i = (tid + q * 256) >> 3;
+        const long m = m0 + i;
+        pa_off[q] = 0; pa_y[q] = -(1 << 20); pa_x[q] = 0;
+        if (m < M) {
+            const int rel = rel0 + i;
+            const int bb = small_div(rel, hw, r_hw);
+            const int rem = rel - bb * hw;
+            const int oy = small_div(rem, a.OW, r_ow);
+            const int ox = rem - oy * a.OW;
+            if (oy < a.AH && ox < a.AW) {
+                pa_y[q] = oy * a.stride - a.pad; pa_x[q] = ox * a.stride - a.pad;
+                pa_off[q] = ((bb * a.H + pa_y[q]) * a.W + pa_x[q]) * a.Cin;
+            }
+        }
+    }
+    const int Kpad = (a.K + KC - 1) / KC * KC;
+    const int j4 = tid & 7;
+    const u32x4* wrow[B_F4];                            // 16 bytes of a row's chunk: j4 < 4 hi halves, j4 >= 4 lo halves
+#pragma unroll
+    for (int q = 0; q < B_F4; ++q) wrow[q] = reinterpret_cast<const u32x4*>(a.wsplit) + (size_t)(n0 + ((tid + q * 256) >> 3)) * (Kpad / 4) + j4;
+    u32x4 va[A_F4], vb[B_F4];
+    int f_r = 0, f_s = 0, f_c = 0, f_k = 0;
+    int voff[A_F4], woff = 0;
+    auto offsets = [&]() {
+        const int kq = f_k + 4 * j4;
+        const int r = f_r, sft = f_s;
+        const int delta = (r * a.W + sft) * a.Cin + f_c + 4 * j4;
+        const int k_ok = (kq < a.K) ? -1 : 0;
+#pragma unroll
+        for (int q = 0; q < A_F4; ++q) {
+            const int iy = pa_y[q] + r, ix = pa_x[q] + sft;
+            const int ok = k_ok & -(int)((unsigned)iy < (unsigned)a.H) & -(int)((unsigned)ix < (unsigned)a.W);
+            voff[q] = (((pa_off[q] + delta) * 4) & ok) | (OOB & ~ok);
+        }
+        woff = f_k / 4;                                 // uint4 units: a chunk's row is 8 of them
+        if (f_k + KC < Kpad) {
+            f_k += KC;
+            f_c += KC;
+            if (f_c >= a.Cin) { f_c = 0; if (++f_s == a.ksz) { f_s = 0; ++f_r; } }
+        }
+    };
+    auto issue = [&]() {
+#pragma unroll
+        for (int q = 0; q < A_F4; ++q) va[q] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, voff[q], 0, 0);
+#pragma unroll
+        for (int q = 0; q < B_F4; ++q) vb[q] = wrow[q][woff];
+    };
+    const float sa = (float)(1 << EMB_A_SCALE_EXP);
+    auto park = [&]() {
+        int bad = 0;                                    // bit q: slot q holds a value that f16 cannot take
+#pragma unroll
+        for (int q = 0; q < A_F4; ++q) {
+            const f32x4 xv = __builtin_bit_cast(f32x4, va[q]) * sa;       // (the whole vector: a bit_cast of one element read element 0)
+            const float x0 = xv.x, x1 = xv.y, x2 = xv.z, x3 = xv.w;
+            const float mx = fmaxf(fmaxf(fabsf(x0), fabsf(x1)), fmaxf(fabsf(x2), fabsf(x3)));
+            bad |= (mx < EMB_F16_LIMIT) ? 0 : (1 << q);      // (NaN included; a row without a pixel loads zeros only)
+            const _Float16 h0 = (_Float16)x0, h1 = (_Float16)x1, h2 = (_Float16)x2, h3 = (_Float16)x3;
+            const f16x2 h01 = {h0, h1}, h23 = {h2, h3};
+            const f16x2 l01 = {(_Float16)(x0 - (float)h0), (_Float16)(x1 - (float)h1)};
+            const f16x2 l23 = {(_Float16)(x2 - (float)h2), (_Float16)(x3 - (float)h3)};
+            uint32_t* row = &As[((tid + q * 256) >> 3) * PITCH + 2 * j4];
+            *reinterpret_cast<u32x2*>(row) = (u32x2){__builtin_bit_cast(uint32_t, h01), __builtin_bit_cast(uint32_t, h23)};
+            *reinterpret_cast<u32x2*>(row + 16) = (u32x2){__builtin_bit_cast(uint32_t, l01), __builtin_bit_cast(uint32_t, l23)};
+        }
+#pragma unroll
+        for (int q = 0; q < B_F4; ++q) *reinterpret_cast<u32x4*>(&Bs[((tid + q * 256) >> 3) * PITCH + 4 * j4]) = vb[q];
+        if (bad)
+            for (int q = 0; q < A_F4; ++q)
+                if ((bad >> q) & 1) a.flags[b_first + small_div(rel0 + ((tid + q * 256) >> 3), hw, r_hw)] = 1;
+    };
+    const int li = lane & 31, kh = lane >> 5;
+    const uint32_t* pa0 = &As[(wm * 64 + li) * PITCH + 4 * kh];
+    const uint32_t* pa1 = pa0 + 32 * PITCH;
+    const uint32_t* pb = &Bs[(wn * 32 + li) * PITCH + 4 * kh];
+    offsets();
+    issue();
+    offsets();
+    for (int k0 = 0; k0 < Kpad; k0 += KC) {
+        park();
+        __syncthreads();
+        issue();
+        __builtin_amdgcn_sched_barrier(0);
+        offsets();
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const f16x8 ah0 = *reinterpret_cast<const f16x8*>(pa0 + 8 * s), al0 = *reinterpret_cast<const f16x8*>(pa0 + 16 + 8 * s);
+            const f16x8 ah1 = *reinterpret_cast<const f16x8*>(pa1 + 8 * s), al1 = *reinterpret_cast<const f16x8*>(pa1 + 16 + 8 * s);
+            const f16x8 bh = *reinterpret_cast<const f16x8*>(pb + 8 * s), bl = *reinterpret_cast<const f16x8*>(pb + 16 + 8 * s);
+            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah0, bh, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah1, bh, acc1, 0, 0, 0);
+            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah0, bl, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah1, bl, acc1, 0, 0, 0);
+            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al0, bh, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al1, bh, acc1, 0, 0, 0);
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { acc0[i] *= a.out_scale; acc1[i] *= a.out_scale; }
+    conv_epilogue<WM, WN>(a, smem, acc0, acc1, M, m0, n0, rel0, b_first, hw, r_hw, r_ow, wave, lane);
+}
+
+// What conv_split_k takes for granted about the device, checked once per context (a mismatch is an error, not a fallback): lanes
+// (row, k octet) of A and (column, k octet) of B meet in v_mfma_f32_32x32x16_f16 as the kernel's LDS reads assume, lane (column, row
+// group) receives D as conv_epilogue assumes, and an accumulation of K products inside the matrix pipe stays within the allowance of
+// the error bound (2^-22 per addition relative to the sum of the terms' magnitudes: DESIGN.md section 4).  One wave; a, b in lane order.
+__global__ void __launch_bounds__(64) embed_probe_k(const uint4* __restrict__ a, const uint4* __restrict__ b, int steps, float* __restrict__ d)
+{
+    const int lane = threadIdx.x;
+    f32x16 acc;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
+    for (int s = 0; s < steps; ++s)
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a[s * 64 + lane]), __builtin_bit_cast(f16x8, b[s * 64 + lane]), acc, 0, 0, 0);
+    for (int i = 0; i < 16; ++i) d[lane * 16 + i] = acc[i];
+}
 
 // ---------------------------------------------------------------------------------------------------
 // The first layer (7 x 7, stride 2, 3 -> 32 channels on the 150 x 150 chip) straight from the uint8 chips.  Through the generic kernel it
@@ -591,16 +773,95 @@ static void launch_conv(Ctx* c, const ConvArgs& a)
                            a.skip_mode == 1 ? a.skip : nullptr, a.out, items);
     } else if (a.Cout == 32) {
         const dim3 grid((unsigned)((M + 255) / 256), 1);
-        hipLaunchKernelGGL((conv_mfma_k<4, 1>), grid, dim3(256), 0, c->stream, a);
+        if (a.wsplit) hipLaunchKernelGGL((conv_split_k<4, 1>), grid, dim3(256), 0, c->stream, a);
+        else hipLaunchKernelGGL((conv_mfma_k<4, 1>), grid, dim3(256), 0, c->stream, a);
     } else {
         PVF_REQUIRE(a.Cout % 64 == 0, "conv: Cout must be 32 or a multiple of 64");
         const dim3 grid((unsigned)((M + 127) / 128), a.Cout / 64);
-        hipLaunchKernelGGL((conv_mfma_k<2, 2>), grid, dim3(256), 0, c->stream, a);
+        if (a.wsplit) hipLaunchKernelGGL((conv_split_k<2, 2>), grid, dim3(256), 0, c->stream, a);
+        else hipLaunchKernelGGL((conv_mfma_k<2, 2>), grid, dim3(256), 0, c->stream, a);
     }
 }
 
-// d_chips: [n][150][150][3] u8 on device; h_out [n][128]
-void resnet_forward(Ctx* c, const uint8_t* d_chips, int n, float* h_out)
+// ---- embed_probe: the f16 matrix pipe against what conv_split_k assumes (once per context, before the first split forward) ----------
+static uint16_t f16_bits(float v)
+{
+    const _Float16 h = (_Float16)v;                     // host conversion: round to nearest even
+    uint16_t u;
+    memcpy(&u, &h, 2);
+    return u;
+}
+
+// Two cases of K = 2304 (the network's longest chain, 9 x 256) on one 32 x 32 tile, exact sums in double on the host: (1) pseudo-random
+// f16 values of both signs over 2^-10 .. 2^15 -- distinct per (row, k) and (k, column), so a lane map other than the kernel's shows up
+// as an error of the order of the sums; (2) the three split terms of pseudo-random fp32 operands at the scales the kernel uses (hi.hi,
+// hi.lo, lo.hi in one chain).  The worst |pipe - exact| / sum of |terms| of both is kept (pvf_embedder_split_stats: pipe_err) and must
+// stay within the allowance of the bound: K x 2^-22.
+static void embed_probe(Ctx* c)
+{
+    const int steps = 144;
+    const int K = steps * 16;
+    const size_t nh = (size_t)steps * 64 * 8;
+    std::vector<uint16_t> ha(nh), hb(nh);
+    std::vector<double> A((size_t)32 * K), B((size_t)K * 32);
+    uint8_t* dev = nullptr;
+    const size_t fb = nh * 2;
+    HIP_CHECK(hipMalloc((void**)&dev, 2 * fb + 64 * 16 * sizeof(float)));
+    float* d_d = reinterpret_cast<float*>(dev + 2 * fb);
+    float hd[64 * 16];
+    // lane l = 32 h + r of k-step s holds A[r][16 s + 8 h + j] and B[16 s + 8 h + j][r] in element j
+    auto ia = [&](int r, int k) { return ((size_t)(k >> 4) * 64 + ((k >> 3) & 1) * 32 + r) * 8 + (k & 7); };
+    uint64_t st = 0x9e3779b97f4a7c15ull;
+    auto rnd = [&]() { st ^= st << 13; st ^= st >> 7; st ^= st << 17; return (double)(st >> 11) * std::ldexp(1.0, -53); };
+    auto run = [&]() -> double {
+        HIP_CHECK(hipMemcpy(dev, ha.data(), fb, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dev + fb, hb.data(), fb, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(embed_probe_k, dim3(1), dim3(64), 0, c->stream, reinterpret_cast<const uint4*>(dev), reinterpret_cast<const uint4*>(dev + fb),
+                           steps, d_d);
+        HIP_CHECK(hipMemcpyAsync(hd, d_d, sizeof hd, hipMemcpyDeviceToHost, c->stream));
+        HIP_CHECK(hipStreamSynchronize(c->stream));
+        double worst = 0;
+        for (int l = 0; l < 64; ++l)
+            for (int i = 0; i < 16; ++i) {
+                const int col = l & 31, row = (i & 3) + 8 * (i >> 2) + 4 * (l >> 5);
+                double ex = 0, mag = 0;
+                for (int k = 0; k < K; ++k) { const double t = A[(size_t)row * K + k] * B[(size_t)k * 32 + col]; ex += t; mag += std::fabs(t); }
+                worst = std::max(worst, std::fabs((double)hd[l * 16 + i] - ex) / (mag > 0 ? mag : 1.0));
+            }
+        return worst;
+    };
+    auto put = [&](int r, int k, int col, float av, float bv) {
+        ha[ia(r, k)] = f16_bits(av); hb[ia(col, k)] = f16_bits(bv);
+        A[(size_t)r * K + k] = (double)(_Float16)av; B[(size_t)k * 32 + col] = (double)(_Float16)bv;
+    };
+    double worst = 0;
+    // case 1
+    for (int k = 0; k < K; ++k)
+        for (int r = 0; r < 32; ++r) {
+            const float av = (float)((rnd() < 0.5 ? -1 : 1) * std::ldexp(1.0 + rnd(), (int)(rnd() * 25) - 10));
+            const float bv = (float)((rnd() < 0.5 ? -1 : 1) * std::ldexp(1.0 + rnd(), (int)(rnd() * 25) - 10));
+            put(r, k, r, av, bv);
+        }
+    worst = std::max(worst, run());
+    // case 2: k-steps cycle through hi.hi, hi.lo, lo.hi of activations x 2^8 in [0, 2^11) and weights x 2^w in (-2^15, 2^15)
+    for (int k = 0; k < K; ++k)
+        for (int r = 0; r < 32; ++r) {
+            const float x = (float)(rnd() * 2048.0), w = (float)((rnd() * 2 - 1) * 32768.0);
+            const _Float16 xh = (_Float16)x, wh = (_Float16)w;
+            const float xl = x - (float)xh, wl = w - (float)wh;
+            const int term = (k >> 4) % 3;
+            put(r, k, r, term == 2 ? xl : (float)xh, term == 1 ? wl : (float)wh);
+        }
+    worst = std::max(worst, run());
+    (void)hipFree(dev);
+    c->emb_pipe_err = worst;
+    PVF_REQUIRE(worst <= (double)K * std::ldexp(1.0, -22),
+                "embed_probe: v_mfma_f32_32x32x16_f16 does not place or accumulate as the split embedder (conv_split_k) assumes on this device");
+}
+
+// d_chips: [n][150][150][3] u8 on device; h_out [n][128]; split: the convolutions outside the 32-channel stage on conv_split_k, and
+// h_flags[n] = 1 for the faces whose activations left its range
+static void resnet_run(Ctx* c, const uint8_t* d_chips, int n, float* h_out, bool split, int* h_flags)
 {
     const EmbedModel& e = c->emb;
     PVF_REQUIRE(e.loaded, "embedder not loaded");
@@ -647,6 +908,29 @@ void resnet_forward(Ctx* c, const uint8_t* d_chips, int n, float* h_out)
             }
             return L.d_frag;
         };
+        // the split halves of the other layers' weights, made on first use
+        auto wsplit_of = [&](int layer) -> const uint32_t* {
+            ConvLayer& L = c->emb.convs[layer];
+            if (!split || (L.cin == 32 && L.cout == 32 && L.k == 3)) return nullptr;     // (the 32-channel stage stays on conv3x3_c32_k)
+            if (!L.d_wsplit) {
+                const int Kpad = (L.k * L.k * L.cin + 31) / 32 * 32;
+                const int total = L.cout * Kpad;
+                HIP_CHECK(hipMalloc(&L.d_wsplit, (size_t)total * 2 * sizeof(_Float16)));
+                hipLaunchKernelGGL(conv_wsplit_k, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, L.d_w, total, L.w_exp,
+                                   reinterpret_cast<_Float16*>(L.d_wsplit));
+            }
+            return L.d_wsplit;
+        };
+        int* flags = nullptr;
+        if (split) {
+            flags = c->s_emb_flags.as<int>();
+            HIP_CHECK(hipMemsetAsync(flags, 0, (size_t)B * sizeof(int), c->stream));
+        }
+        auto set_split = [&](int layer) {
+            a.wsplit = wsplit_of(layer);
+            a.out_scale = std::ldexp(1.0f, -(EMB_A_SCALE_EXP + c->emb.convs[layer].w_exp));
+            a.flags = flags;
+        };
         for (int u = 0; u < 14; ++u) {
             const int cin = UN[u][0], nn = UN[u][1], down = UN[u][2];
             const ConvLayer& La = e.convs[1 + 2 * u];
@@ -657,6 +941,7 @@ void resnet_forward(Ctx* c, const uint8_t* d_chips, int n, float* h_out)
             a.in = cur; a.B = B; a.H = H; a.W = W; a.Cin = cin; a.w = La.d_w; a.K = 9 * cin; a.bias = La.d_bias; a.gamma = La.d_gamma; a.beta = La.d_beta;
             a.out = t1; a.OH = ah; a.OW = aw; a.Cout = nn; a.AH = ah; a.AW = aw; a.ksz = 3; a.stride = stride; a.pad = pad; a.relu = 1; a.skip_mode = 0;
             a.frag = frag_of(1 + 2 * u);
+            set_split(1 + 2 * u);
             launch_conv(c, a);
             int sh = H, sw = W;
             if (down) { sh = 1 + (H - 2) / 2; sw = 1 + (W - 2) / 2; }
@@ -666,6 +951,7 @@ void resnet_forward(Ctx* c, const uint8_t* d_chips, int n, float* h_out)
             a.out = t2; a.OH = oh; a.OW = ow; a.Cout = nn; a.AH = ah; a.AW = aw; a.ksz = 3; a.stride = 1; a.pad = 1; a.relu = 1;
             a.skip_mode = down ? 2 : 1; a.skip = cur; a.XH = H; a.XW = W; a.XC = cin; a.SH = sh; a.SW = sw;
             a.frag = frag_of(2 + 2 * u);
+            set_split(2 + 2 * u);
             launch_conv(c, a);
             float* old = cur; cur = t2; t2 = old;
             H = oh; W = ow;
@@ -675,6 +961,31 @@ void resnet_forward(Ctx* c, const uint8_t* d_chips, int n, float* h_out)
         hipLaunchKernelGGL(head_k, dim3(B), dim3(256), 0, c->stream, cur, H * W, e.d_fc, d_out);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipMemcpyAsync(h_out + (size_t)b0 * 128, d_out, (size_t)B * 128 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        if (split) HIP_CHECK(hipMemcpyAsync(h_flags + b0, flags, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     }
     HIP_CHECK(hipStreamSynchronize(c->stream));
+}
+
+// The split forward, then the faces it flagged once more through the exact kernels alone (their descriptors are then the exact path's,
+// bit for bit: every kernel computes each face on its own)
+void resnet_forward(Ctx* c, const uint8_t* d_chips, int n, float* h_out)
+{
+    if (!c->emb_split) { resnet_run(c, d_chips, n, h_out, false, nullptr); return; }
+    if (!c->emb_probe_done) { embed_probe(c); c->emb_probe_done = true; }
+    c->s_emb_flags.ensure((size_t)std::min(n, 4096) * sizeof(int));
+    std::vector<int> flags(n, 0);
+    resnet_run(c, d_chips, n, h_out, true, flags.data());
+    c->emb_split_faces += n;
+    std::vector<int> redo;
+    for (int i = 0; i < n; ++i) if (flags[i]) redo.push_back(i);
+    if (redo.empty()) return;
+    c->emb_reruns += (int64_t)redo.size();
+    const size_t chip = (size_t)150 * 150 * 3;
+    c->s_emb_redo.ensure(redo.size() * chip);
+    uint8_t* d = c->s_emb_redo.as<uint8_t>();
+    for (size_t j = 0; j < redo.size(); ++j)
+        HIP_CHECK(hipMemcpyAsync(d + j * chip, d_chips + (size_t)redo[j] * chip, chip, hipMemcpyDeviceToDevice, c->stream));
+    std::vector<float> e(redo.size() * 128);
+    resnet_run(c, d, (int)redo.size(), e.data(), false, nullptr);
+    for (size_t j = 0; j < redo.size(); ++j) memcpy(h_out + (size_t)redo[j] * 128, e.data() + j * 128, 128 * sizeof(float));
 }

@@ -715,6 +715,20 @@ class Context(object):
         check(self._l.pvf_detector_screening_stats(self._h, C.byref(b), C.byref(n), C.byref(r), ptr(bounds), C.byref(pe)))
         return {"batches": b.value, "listed": n.value, "retries": r.value, "bounds": bounds[:5].tolist(), "pipe_err": pe.value}
 
+    def embedder_split(self, on=True):
+        """the embedder's convolutions on the f16 matrix cores with split operands (csrc/resnet.hip: conv_split_k; on by default): three
+        f16 products of scaled hi / lo halves per product, descriptors within the bound of DESIGN.md section 4; a face whose activations
+        leave the f16 range is embedded again on the exact fp32 kernels.  off: the exact kernels only"""
+        check(self._l.pvf_embedder_split(self._h, 1 if on else 0))
+
+    def embedder_split_stats(self):
+        """{"faces", "reruns", "pipe_err"}: faces embedded with the split on, faces of those embedded again on the exact kernels, the
+        accumulation error the context measured on its f16 matrix pipe (relative to the sum of magnitudes; -1 before the first split
+        forward)"""
+        f, r, pe = C.c_int64(0), C.c_int64(0), C.c_double(-1.0)
+        check(self._l.pvf_embedder_split_stats(self._h, C.byref(f), C.byref(r), C.byref(pe)))
+        return {"faces": f.value, "reruns": r.value, "pipe_err": pe.value}
+
     def prof_enable(self, on=True):
         check(self._l.pvf_prof_enable(self._h, 1 if on else 0))
 
