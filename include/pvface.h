@@ -93,6 +93,19 @@ int32_t pvf_ingest_destroy(pvf_handle ctx, pvf_handle ring);
 int32_t pvf_ingest_acquire(pvf_handle ctx, pvf_handle ring, int32_t* slot, uint8_t** host_rgb);
 int32_t pvf_ingest_submit(pvf_handle ctx, pvf_handle ring, int32_t slot, pvf_handle* frame);
 int32_t pvf_ingest_wait(pvf_handle ctx, pvf_handle ring);       /* all queued uploads done (measurement, shutdown) */
+/* YUV at ingest ("YUV to RGB"): what a decoder writes -- 8-bit 4:2:0 / 4:2:2 / 4:4:4 -- goes to HBM as it is
+ * (1.5 bytes per pixel over PCIe for 4:2:0 where RGB takes 3) and one kernel writes the RGB frame every other call reads.  The
+ * reference leaves this to `ffmpeg -pix_fmt rgb24` on the CPU (video.py:332-358).  Integer 16.16 arithmetic, chroma replicated. */
+#define PVF_YUV_BT709 1        /* flags: BT.709 matrix (default BT.601) */
+#define PVF_YUV_FULL_RANGE 2   /* flags: full range 0..255 (default limited: Y 16..235) */
+/* a ring like pvf_ingest_create's whose slots hold one planar frame: Y (h x w), U, V (ceil(w / 2) x ceil(h / 2) each for layout 420;
+ * 422 halves the width only, 444 neither), tight, in that order; acquire / submit / wait / destroy work on it unchanged, and submit
+ * queues copy + conversion on the ring's copy stream */
+int32_t pvf_ingest_create_yuv(pvf_handle ctx, int32_t h, int32_t w, int32_t depth, int32_t layout, int32_t flags, pvf_handle* ring);
+/* planes already in HBM (a hardware decoder's surface): pitches in bytes; c_step 1 = planar chroma, 2 = interleaved (NV12: u = uv,
+ * v = uv + 1).  Returns when the planes have been read: the surface may be reused at once.  The frame is the library's own (pooled). */
+int32_t pvf_frame_from_yuv(pvf_handle ctx, const uint8_t* y, int64_t y_pitch, const uint8_t* u, const uint8_t* v, int64_t c_pitch,
+                           int32_t c_step, int32_t h, int32_t w, int32_t layout, int32_t flags, pvf_handle* frame);
 /* ref: video.py:180-187,402-403 + tracking.py:389-400  cv2.resize(frame, (w, h)) for detection on down-scaled frames (--min-size):
  * OpenCV's 8-bit INTER_LINEAR on the device; the source frame stays resident for `extract` */
 int32_t pvf_frame_resize(pvf_handle ctx, pvf_handle frame, int32_t out_w, int32_t out_h, pvf_handle* out);

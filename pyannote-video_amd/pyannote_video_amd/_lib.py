@@ -54,6 +54,8 @@ _SIGS = {
     "pvf_ingest_acquire": (C.c_int32, [H, H, P, P]),
     "pvf_ingest_submit": (C.c_int32, [H, H, C.c_int32, P]),
     "pvf_ingest_wait": (C.c_int32, [H, H]),
+    "pvf_ingest_create_yuv": (C.c_int32, [H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P]),
+    "pvf_frame_from_yuv": (C.c_int32, [H, P, C.c_int64, P, P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P]),
     "pvf_frame_resize": (C.c_int32, [H, H, C.c_int32, C.c_int32, P]),
     "pvf_detect": (C.c_int32, [H, H, C.c_int32, C.c_double, P, P, C.c_int32, P]),
     "pvf_detect_batch": (C.c_int32, [H, P, C.c_int32, C.c_int32, C.c_double, P, P, P, C.c_int32]),

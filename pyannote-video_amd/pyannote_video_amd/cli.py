@@ -12,9 +12,14 @@ embedding.txt: formats.py).  `cluster` is the verb BASELINE.json's north_star na
 only (face/clustering.py:130-134).  It writes `identifier label` lines, the file `demo --label` reads (pyannote-face.py:87,391-397).
 `demo` (video rendering through moviepy) is out of scope.
 
-<video>: decoding through ffmpeg (reference video.py:345-406) is not part of this path; the verbs read frames that are already
-decoded -- a `.npy` file holding uint8 [N, H, W, 3] RGB frames (memory mapped; frame rate from --fps) -- or render the bench's
-synthetic clip: `synthetic:<width>x<height>x<frames>[:shots[:faces[:seed]]]`.
+<video>: no codec is linked (reference video.py:345-406 runs ffmpeg); the verbs read what a decoder writes --
+  * a YUV4MPEG2 file (`.y4m`, or any file that starts with `YUV4MPEG2`): 8-bit 4:2:0 / 4:2:2 / 4:4:4, memory mapped, frame rate from
+    its header (`ffmpeg -i film.mkv -pix_fmt yuv420p -f yuv4mpegpipe film.y4m`); the planes go to the GPU as they are and are
+    converted to RGB there (--matrix 601|709, --range limited|full override the header);
+  * `-`: the same stream from stdin, for the verbs that read the video once and need no length (`track`, `process`):
+    `ffmpeg -i film.mkv -pix_fmt yuv420p -f yuv4mpegpipe - | python -m pyannote_video_amd process - ...`;
+  * a `.npy` file holding uint8 [N, H, W, 3] RGB frames (memory mapped; frame rate from --fps);
+  * the bench's synthetic clip: `synthetic:<width>x<height>x<frames>[:shots[:faces[:seed]]]`.
 <shot.json>: a JSON list of [start, end] seconds (what pyannote.core.json holds for a Timeline reduces to this for our purpose).
 """
 import argparse
@@ -71,7 +76,11 @@ class NpyVideo(object):
         return self.frame(i)
 
 
-def open_video(spec, frame_rate):
+def open_video(spec, frame_rate, matrix=None, full_range=None):
+    """matrix ('601' / '709') and full_range (bool) override what a Y4M header says; None leaves it to the header"""
+    if spec == "-":
+        from .y4m import Y4mVideo
+        return Y4mVideo(sys.stdin.buffer, frame_rate, matrix=matrix, full_range=full_range)
     if spec.startswith("synthetic:"):
         from . import synth
         parts = spec[len("synthetic:"):].split(":")
@@ -80,6 +89,9 @@ def open_video(spec, frame_rate):
         for name, val in zip(("n_shots", "faces", "seed"), parts[1:]):
             kw[name] = int(val)
         return synth.SyntheticVideo(width=w, height=h, n_frames=n, frame_rate=frame_rate, **kw)
+    from . import y4m
+    if y4m.is_y4m(spec):
+        return y4m.Y4mVideo(spec, frame_rate, matrix=matrix, full_range=full_range)
     return NpyVideo(spec, frame_rate)
 
 
@@ -153,22 +165,16 @@ def extract(video, landmark_model, embedding_model, tracking, landmark_output, e
     state = {"error": None}
 
     def reader():
-        ring = None
+        stager = runtime.HostFrameStager(ctx, 16)
         try:
             for fi, (t, rgb) in enumerate(video):
                 if fi > last_wanted:
                     break
                 if fi not in want:
                     continue
-                owned = False
-                if not isinstance(rgb, runtime.DeviceFrame):
-                    if ring is None:
-                        ring = ctx.ingest_ring(rgb.shape[0], rgb.shape[1], depth=16)
-                    rgb = ring.push(rgb)
-                    owned = True
+                rgb, owned = stager.stage(rgb)
                 q.put((fi, rgb, owned))
-            if ring is not None:
-                ring.close()
+            stager.close()
         except BaseException as e:          # noqa: BLE001 -- re-raised below
             state["error"] = e
         finally:
@@ -310,7 +316,10 @@ def thread(video, shot, output, min_match=20, lookahead=24, ctx=None):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="pyannote-face", description="face tracking => feature extraction => face clustering (MI355X)")
-    ap.add_argument("--fps", type=float, default=25.0, help="frame rate of a .npy / synthetic video")
+    ap.add_argument("--fps", type=float, default=25.0, help="frame rate of a .npy / synthetic video (Y4M: only if its header names none)")
+    ap.add_argument("--matrix", choices=("601", "709"), default=None, help="YUV matrix of a Y4M video (its header cannot name one; default BT.601)")
+    ap.add_argument("--range", choices=("limited", "full"), default=None, help="sample range of a Y4M video (default: XCOLORRANGE of its "
+                    "header, else limited)")
     ap.add_argument("--device", type=int, default=None, help="GPU index (default: LOCAL_RANK or 0)")
     ap.add_argument("--metrics", default=None, help="write a JSON file with the run's timings and counts (frames, tracks, faces, seconds per stage, "
                     "frames resident at peak, device memory in use) next to the outputs")
@@ -358,19 +367,29 @@ def main(argv=None):
         ctx = Context(device=a.device)
     t_begin = time.perf_counter()
     res = None
+
+    def video():
+        if a.video == "-" and a.verb not in ("track", "process"):
+            ap.error("%s needs the length of the video: give it a file, not a stream on stdin" % a.verb)
+        over = {}
+        if a.matrix is not None:
+            over["matrix"] = a.matrix
+        if a.range is not None:
+            over["full_range"] = a.range == "full"
+        return open_video(a.video, a.fps, **over)
     if a.verb == "track":
-        res = track(open_video(a.video, a.fps), a.shot, a.tracking, detect_min_size=a.min_size, detect_every=a.every,
+        res = track(video(), a.shot, a.tracking, detect_min_size=a.min_size, detect_every=a.every,
                     track_min_overlap_ratio=a.min_overlap, track_min_confidence=a.min_confidence, track_max_gap=a.max_gap, ctx=ctx)
     elif a.verb == "process":
-        res = process(open_video(a.video, a.fps), a.shot, a.landmark_model, a.embedding_model, a.tracking, a.landmarks, a.embeddings, a.labels,
+        res = process(video(), a.shot, a.landmark_model, a.embedding_model, a.tracking, a.landmarks, a.embeddings, a.labels,
                 detect_min_size=a.min_size, detect_every=a.every, track_min_overlap_ratio=a.min_overlap,
                 track_min_confidence=a.min_confidence, track_max_gap=a.max_gap, threshold=a.threshold, ctx=ctx)
     elif a.verb == "shot":
-        shot(open_video(a.video, a.fps), a.output, height=a.height, window=a.window, threshold=a.threshold, ctx=ctx)
+        shot(video(), a.output, height=a.height, window=a.window, threshold=a.threshold, ctx=ctx)
     elif a.verb == "thread":
-        thread(open_video(a.video, a.fps), a.shot, a.output, min_match=a.min_match, lookahead=a.lookahead, ctx=ctx)
+        thread(video(), a.shot, a.output, min_match=a.min_match, lookahead=a.lookahead, ctx=ctx)
     elif a.verb == "extract":
-        extract(open_video(a.video, a.fps), a.landmark_model, a.embedding_model, a.tracking, a.landmarks, a.embeddings, ctx=ctx)
+        extract(video(), a.landmark_model, a.embedding_model, a.tracking, a.landmarks, a.embeddings, ctx=ctx)
     else:
         cluster(a.embeddings, a.labels, threshold=a.threshold, force=a.force, metric=a.metric, ctx=ctx)
     if a.metrics:

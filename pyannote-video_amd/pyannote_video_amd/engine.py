@@ -25,6 +25,7 @@ import time as _time
 import numpy as np
 
 from . import formats
+from .runtime import HostFrameStager
 from .tracking_by_detection import get_segment_generator, HipTrackers
 
 
@@ -1077,7 +1078,8 @@ def resident_source(job, frames, times, shots, every, resize=None):
 class StreamSource(object):
     """Reads `video` (an iterable of (t, frame): numpy uint8 [H, W, 3] or DeviceFrame) in a thread of its own, cuts it into shots by the
     reference's flush rule and hands complete shots to the engine through a bounded queue.  numpy frames reach HBM through a pinned
-    ingest ring (one asynchronous copy each on the copy stream; the reference's `Video.__iter__` + `np.fromstring`, video.py:368-406);
+    ingest ring (one asynchronous copy each on the copy stream; the reference's `Video.__iter__` + `np.fromstring`, video.py:368-406),
+    the YuvFrames of a Y4M video through a YUV ring (planes copied as they are, RGB made on the device: runtime.HostFrameStager);
     the frames it staged are the engine's to release."""
 
     def __init__(self, ctx, jobs, depth=1, ring_depth=24):
@@ -1096,7 +1098,7 @@ class StreamSource(object):
             for job, video, shots, every, resize in self.jobs:
                 seg = get_segment_generator(shots)
                 seg.send(None)
-                ring = None
+                stager = HostFrameStager(self.ctx, self.ring_depth)
                 cache, flags, base, i, owned = [], [], 0, 0, False
                 for t, frame in video:
                     if self._stop:
@@ -1104,21 +1106,15 @@ class StreamSource(object):
                     if seg.send(t):
                         self.q.put(ShotInput(job, base, cache, flags, owned=owned, resize=resize))
                         cache, flags, base = [], [], i
-                    if isinstance(frame, np.ndarray):
-                        if ring is None or (ring.h, ring.w) != frame.shape[:2]:
-                            if ring is not None:
-                                ring.close()
-                            ring = self.ctx.ingest_ring(frame.shape[0], frame.shape[1], depth=self.ring_depth)
-                        frame = ring.push(frame)
-                        owned = True
+                    frame, staged = stager.stage(frame)
+                    owned = owned or staged
                     cache.append((t, frame))
                     flags.append(i % every == 0)
                     i += 1
                     self.frames_read += 1
                 self.q.put(ShotInput(job, base, cache, flags, owned=owned, resize=resize))
                 self.q.put(JobEnd(job))
-                if ring is not None:
-                    ring.close()              # waits for the last uploads
+                stager.close()                # waits for the last uploads
         except BaseException as e:              # noqa: BLE001 -- re-raised in the consumer
             self.error = e
         finally:

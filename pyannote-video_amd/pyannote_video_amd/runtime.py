@@ -8,6 +8,7 @@ import numpy as np
 from . import _lib
 from ._lib import check, ptr, handles
 from . import models as _models
+from .y4m import YuvFrame, chroma_shape
 
 
 class DeviceFrame(object):
@@ -79,6 +80,90 @@ class IngestRing(object):
             pass
 
 
+_YUV_LAYOUTS = {"420": 420, "422": 422, "444": 444}
+
+
+def _yuv_flags(matrix, full_range):
+    if str(matrix) not in ("601", "709"):
+        raise ValueError("matrix must be '601' or '709', not %r" % (matrix,))
+    return (1 if str(matrix) == "709" else 0) | (2 if full_range else 0)       # PVF_YUV_BT709, PVF_YUV_FULL_RANGE
+
+
+def _yuv_layout(layout):
+    if str(layout) not in _YUV_LAYOUTS:
+        raise ValueError("layout must be '420', '422' or '444', not %r" % (layout,))
+    return _YUV_LAYOUTS[str(layout)]
+
+
+class YuvIngestRing(IngestRing):
+    """An ingest ring whose pinned slots hold the planes a decoder writes (pvf_ingest_create_yuv): `slot()` hands out the (Y, U, V) views
+    of the next slot, `submit()` queues one copy of the planes and the conversion kernel on the copy stream and returns the RGB
+    DeviceFrame at once.  4:2:0 crosses PCIe with half the bytes of RGB."""
+
+    def __init__(self, ctx, height, width, layout="420", matrix="601", full_range=False, depth=8):
+        self.ctx, self.h, self.w, self.depth = ctx, int(height), int(width), int(depth)
+        self.layout, self.matrix, self.full_range = str(layout), str(matrix), bool(full_range)
+        self._r = None
+        code, flags = _yuv_layout(layout), _yuv_flags(matrix, full_range)
+        r = C.c_uint64(0)
+        check(ctx._l.pvf_ingest_create_yuv(ctx._h, self.h, self.w, self.depth, code, flags, C.byref(r)))
+        self._r = r.value
+        self._cur = None
+        self._ch, self._cw = chroma_shape(self.h, self.w, self.layout)
+
+    def slot(self):
+        s, p = C.c_int32(0), C.c_void_p(0)
+        check(self.ctx._l.pvf_ingest_acquire(self.ctx._h, self._r, C.byref(s), C.byref(p)))
+        self._cur = s.value
+        ny, nc = self.h * self.w, self._ch * self._cw
+        a = np.frombuffer((C.c_uint8 * (ny + 2 * nc)).from_address(p.value), np.uint8)
+        return (a[:ny].reshape(self.h, self.w), a[ny:ny + nc].reshape(self._ch, self._cw), a[ny + nc:].reshape(self._ch, self._cw))
+
+    def push(self, frame):
+        """copy a YuvFrame's planes into the next slot and queue upload + conversion"""
+        if (frame.height, frame.width, frame.layout, frame.matrix, frame.full_range) != (self.h, self.w, self.layout, self.matrix, self.full_range):
+            raise ValueError("this ring was made for %dx%d %s frames (matrix %s, %s range)" % (
+                self.w, self.h, self.layout, self.matrix, "full" if self.full_range else "limited"))
+        y, u, v = self.slot()
+        np.copyto(y, frame.y)
+        np.copyto(u, frame.u)
+        np.copyto(v, frame.v)
+        return self.submit()
+
+
+class HostFrameStager(object):
+    """What a reader thread does with the frames a video yields: numpy RGB frames go through a pinned RGB ring, YuvFrames through a YUV
+    ring (made when the first such frame arrives, remade when the geometry changes); anything else -- a DeviceFrame -- is passed on
+    as it is.  stage(frame) -> (frame for the engine, True if this object made it and the consumer has to release it)."""
+
+    def __init__(self, ctx, depth):
+        self.ctx, self.depth = ctx, int(depth)
+        self._ring, self._key = None, None
+
+    def stage(self, frame):
+        if isinstance(frame, YuvFrame):
+            key = ("yuv",) + frame.key
+        elif isinstance(frame, np.ndarray):
+            key = ("rgb",) + tuple(frame.shape[:2])
+        else:
+            return frame, False
+        if key != self._key:
+            self.close()
+            if key[0] == "yuv":
+                self._ring = self.ctx.ingest_ring_yuv(frame.height, frame.width, layout=frame.layout, matrix=frame.matrix,
+                                                      full_range=frame.full_range, depth=self.depth)
+            else:
+                self._ring = self.ctx.ingest_ring(frame.shape[0], frame.shape[1], depth=self.depth)
+            self._key = key
+        return self._ring.push(frame), True
+
+    def close(self):
+        """waits for the last uploads"""
+        if self._ring is not None:
+            self._ring.close()
+        self._ring, self._key = None, None
+
+
 def _boxes_and_scores(out, scores, counts):
     """[( [(l, t, r, b) Python ints], float32 scores )] per frame.  One tolist() for the whole batch: indexing numpy rows element by
     element cost 3 ms per 250-frame shot, during which the GPU had nothing queued."""
@@ -135,6 +220,7 @@ class Context(object):
         self._stage_mu = threading.RLock()   # the staging cache is used from the detector thread and the tracker / extraction threads
         self._tables = False
         self._models = {}
+        self._yuv_rings = {}   # YuvFrame.key -> YuvIngestRing of upload(): made on first use, closed with the context
         if detector:
             self.load_detector(detector)
         if landmarks:
@@ -147,6 +233,8 @@ class Context(object):
             for f in list(self._staged.values()):
                 f.release()
             self._staged.clear()
+            for r in self.__dict__.pop("_yuv_rings", {}).values():
+                r.close()
             self._l.pvf_ctx_destroy(self._h)
             self._h = None
 
@@ -195,6 +283,13 @@ class Context(object):
 
     # ---- frames
     def upload(self, rgb):
+        """a host frame to HBM: a numpy RGB frame as it is, a YuvFrame (y4m.py) through a small YUV ring and the conversion kernel"""
+        if isinstance(rgb, YuvFrame):
+            with self._stage_mu:
+                ring = self._yuv_rings.get(rgb.key)
+                if ring is None:
+                    ring = self._yuv_rings[rgb.key] = self.ingest_ring_yuv(rgb.height, rgb.width, rgb.layout, rgb.matrix, rgb.full_range, depth=4)
+                return ring.push(rgb)
         rgb = np.asarray(rgb)
         if rgb.dtype != np.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3:
             raise TypeError("frames must be uint8 arrays of shape (H, W, 3)")   # dlib raises on unsupported arrays too
@@ -249,6 +344,33 @@ class Context(object):
 
     def ingest_ring(self, height, width, depth=8):
         return IngestRing(self, height, width, depth)
+
+    def ingest_ring_yuv(self, height, width, layout="420", matrix="601", full_range=False, depth=8):
+        return YuvIngestRing(self, height, width, layout, matrix, full_range, depth)
+
+    def frame_from_yuv_device(self, y_ptr, y_pitch, u_ptr, v_ptr, c_pitch, height, width, layout="420", matrix="601", full_range=False,
+                              c_step=1):
+        """RGB DeviceFrame from planes that already lie in HBM (a hardware decoder's surface): pitches in bytes, c_step 2 for
+        interleaved chroma (NV12: v_ptr = u_ptr + 1).  The planes have been read when the call returns."""
+        h = C.c_uint64(0)
+        check(self._l.pvf_frame_from_yuv(self._h, C.c_void_p(int(y_ptr)), int(y_pitch), C.c_void_p(int(u_ptr)), C.c_void_p(int(v_ptr)),
+                                         int(c_pitch), int(c_step), int(height), int(width), _yuv_layout(layout),
+                                         _yuv_flags(matrix, full_range), C.byref(h)))
+        return DeviceFrame(self, h.value, int(height), int(width))
+
+    def frame_from_yuv_torch(self, y, u, v=None, layout="420", matrix="601", full_range=False):
+        """y: torch.uint8 CUDA tensor [H, W]; u, v: the chroma planes [CH, CW], or u = interleaved [CH, CW, 2] and v = None (NV12).
+        Rows may be strided (a view of a pitched surface); the samples of a row are contiguous.  The caller makes sure the tensors
+        are written (torch.cuda.synchronize or a stream wait) before the call."""
+        for t in (y, u) + (() if v is None else (v,)):
+            assert t.is_cuda and t.element_size() == 1 and t.stride(-1) == 1
+        if v is None:
+            assert u.dim() == 3 and u.shape[2] == 2 and (u.shape[1] == 1 or u.stride(1) == 2)
+            return self.frame_from_yuv_device(y.data_ptr(), y.stride(0), u.data_ptr(), u.data_ptr() + 1, u.stride(0), y.shape[0], y.shape[1],
+                                              layout, matrix, full_range, c_step=2)
+        assert u.dim() == 2 and v.dim() == 2 and u.shape == v.shape and u.stride(0) == v.stride(0)
+        return self.frame_from_yuv_device(y.data_ptr(), y.stride(0), u.data_ptr(), v.data_ptr(), u.stride(0), y.shape[0], y.shape[1],
+                                          layout, matrix, full_range)
 
     def stage(self, rgb):
         """DeviceFrame for whatever the caller holds: DeviceFrame (as is) or numpy array (uploaded once, cached by identity)."""
