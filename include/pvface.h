@@ -330,6 +330,23 @@ int32_t pvf_debug_detect_raw_many(pvf_handle ctx, const pvf_handle* frames, int3
 int32_t pvf_debug_extract_chip(pvf_handle ctx, pvf_handle frame, const double rect[4], double cs, double sn,
                                int32_t rows, int32_t cols, uint8_t* out);
 int32_t pvf_debug_tracker_state(pvf_handle ctx, pvf_handle trk, double* F, double* A, double* B);
+/* The embedder's forward as pvf_embed_chips runs it (split != 0: the f16 split path, without the exact second pass of flagged faces),
+ * with the activation after `stage` copied out as out [n][dims[0]][dims[1]][dims[2]] fp32: stage 0 the first layer, 1 the max-pool,
+ * 2 + 2u the `a` layer and 3 + 2u the output of residual unit u = 0..13 (30 stages; head_k, which averages and multiplies in one
+ * kernel, is reached through pvf_debug_embed_head).  out == NULL: dims only, nothing runs.
+ * flags [n] (may be NULL; split only): 1 for a face that left the f16 range.  n <= 4096. */
+int32_t pvf_debug_embed_stage(pvf_handle ctx, const uint8_t* chips, int32_t n, int32_t split, int32_t stage, float* out, int32_t dims[3],
+                              int32_t* flags);
+/* ONE convolution layer (bias, affine, skip, ReLU) through the embedder's launcher on tensors of the caller, weights prepared by the
+ * code the model loader uses.  geom = {B, H, W, Cin, OH, OW, Cout, AH, AW, ksz, stride, pad, skip_mode, XH, XW, XC, SH, SW}: in
+ * [B][H][W][Cin], w [Cout][Cin][ksz][ksz], out [B][OH][OW][Cout] (conv results in [AH][AW], zero-extended), skip_mode 0 none,
+ * 1 skip [B][OH][OW][Cout], 2 the 2 x 2 stride-2 average of skip [B][XH][XW][XC] added to [SH][SW] x the first XC channels.
+ * split: the f16 split kernels where the product would use them, flags [B] (may be NULL) as above.  force_generic: never the
+ * dedicated 35 x 35 x 32 kernel.  A shape the launcher does not take is an error; the context stays usable. */
+int32_t pvf_debug_conv(pvf_handle ctx, const int32_t geom[18], const float* in, const float* w, const float* bias, const float* gamma,
+                       const float* beta, const float* skip, int32_t split, int32_t force_generic, float* out, int32_t* flags);
+/* head_k on x [n][hw][256] with the loaded model's 256 x 128 matrix: out [n][128] */
+int32_t pvf_debug_embed_head(pvf_handle ctx, const float* x, int32_t n, int32_t hw, float* out);
 
 /* ---- f4: shot boundary detection ------------------------------------------------------------------
  * ref: pyannote/video/structure/shot.py:71-73 (_convert: RGB -> gray -> cv2.resize to `width` x `height`), :75-99 (dfd: Farneback flow

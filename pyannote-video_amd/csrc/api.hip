@@ -736,6 +736,41 @@ extern "C" int32_t pvf_debug_extract_chip(pvf_handle h, pvf_handle frame, const 
     API_END
 }
 
+extern "C" int32_t pvf_debug_embed_stage(pvf_handle h, const uint8_t* chips, int32_t n, int32_t split, int32_t stage, float* out, int32_t dims[3],
+                                         int32_t* flags)
+{
+    API_BEGIN
+    ENTER(c, h);
+    PVF_REQUIRE(dims && n > 0 && n <= 4096 && (chips || !out), "pvf_debug_embed_stage: bad arguments");
+    EmbedTap tap{stage, out, {0, 0, 0}};
+    if (out) {
+        const size_t bytes = (size_t)n * 150 * 150 * 3;
+        c->s_trk0.ensure(bytes);
+        HIP_CHECK(hipMemcpyAsync(c->s_trk0.p, chips, bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    resnet_debug_stage(c, c->s_trk0.as<uint8_t>(), n, split != 0, &tap, flags);
+    for (int i = 0; i < 3; ++i) dims[i] = tap.dims[i];
+    API_END
+}
+
+extern "C" int32_t pvf_debug_conv(pvf_handle h, const int32_t geom[18], const float* in, const float* w, const float* bias, const float* gamma,
+                                  const float* beta, const float* skip, int32_t split, int32_t force_generic, float* out, int32_t* flags)
+{
+    API_BEGIN
+    ENTER(c, h);
+    PVF_REQUIRE(geom, "pvf_debug_conv: bad arguments");
+    resnet_debug_conv(c, geom, in, w, bias, gamma, beta, skip, split != 0, force_generic != 0, out, flags);
+    API_END
+}
+
+extern "C" int32_t pvf_debug_embed_head(pvf_handle h, const float* x, int32_t n, int32_t hw, float* out)
+{
+    API_BEGIN
+    ENTER(c, h);
+    resnet_debug_head(c, x, n, hw, out);
+    API_END
+}
+
 // ---- S5 -------------------------------------------------------------------------------------------
 static PairInput table_f64(const double* X) { PairInput in; in.X = X; return in; }
 static PairOutput host_full(double* D) { PairOutput o; o.out = D; return o; }

@@ -388,6 +388,17 @@ void ert_run(Ctx* c, const std::vector<Frame>& frames, const pvf_rect_i32* boxes
 // embedding (resnet.hip)
 void face_chip_details(const EmbedModel& m, const int32_t* pts68, ChipDetails* out);
 void resnet_forward(Ctx* c, const uint8_t* d_chips, int n, float* h_out);
+// a layer's weights on the device as the convolution kernels read them: w [cout][cin][k][k] -> d_w ([cout][K padded to 32], k = (r, s, c)
+// with the 3-channel layer's fourth all-zero channel), w_exp, and bias / gamma / beta; conv_layer_free releases everything the layer holds
+void conv_layer_upload(ConvLayer& L, const float* w, const float* bias, const float* gamma, const float* beta);
+void conv_layer_free(ConvLayer& L);
+// stage access (pvf_debug_embed_stage, pvf_debug_conv, pvf_debug_embed_head)
+#define EMB_STAGES 30   // 0 first layer, 1 max-pool, 2 + 2u / 3 + 2u the `a` layer / the output of unit u
+struct EmbedTap { int stage; float* h_out; int dims[3]; };             // h_out [n][H][W][C] or null: dims only is answered without a run
+void resnet_debug_stage(Ctx* c, const uint8_t* d_chips, int n, bool split, EmbedTap* tap, int* h_flags);
+void resnet_debug_conv(Ctx* c, const int32_t* geom, const float* in, const float* w, const float* bias, const float* gamma, const float* beta,
+                       const float* skip, bool split, bool force_generic, float* out, int32_t* flags);
+void resnet_debug_head(Ctx* c, const float* x, int n, int hw, float* out);
 // tracker (dsst.hip)
 void dsst_start_many(Ctx* c, const std::vector<Tracker*>& t, const std::vector<Frame>& f, const double* boxes);
 void dsst_clone_many(Ctx* c, const std::vector<Tracker*>& src, const std::vector<Tracker*>& dst);

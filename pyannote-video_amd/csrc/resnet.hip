@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <vector>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -58,7 +59,6 @@ struct ConvArgs {
     float* out; int OH, OW, Cout;      // output tensor dims
     int AH, AW;                        // conv-valid dims (<= OH, OW)
     int ksz, stride, pad;
-    int relu;
     int skip_mode;                     // 0 none, 1 identity [B][OH][OW][Cout], 2 avg-pool 2x2 s2 of x [B][XH][XW][XC]
     const float* skip; int XH, XW, XC, SH, SW;
     // split path (conv_split_k): the weights as f16 hi / lo halves of (w * 2^w_exp), [Cout][Kpad / 32][32 hi, 32 lo]; activations are
@@ -128,7 +128,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, float* smem, co
                 const float4 sk = *reinterpret_cast<const float4*>(a.skip + (size_t)m * a.Cout + cb);
                 v.x += sk.x; v.y += sk.y; v.z += sk.z; v.w += sk.w;
             }
-            if (a.relu) { v.x = v.x < 0.0f ? 0.0f : v.x; v.y = v.y < 0.0f ? 0.0f : v.y; v.z = v.z < 0.0f ? 0.0f : v.z; v.w = v.w < 0.0f ? 0.0f : v.w; }
+            { v.x = v.x < 0.0f ? 0.0f : v.x; v.y = v.y < 0.0f ? 0.0f : v.y; v.z = v.z < 0.0f ? 0.0f : v.z; v.w = v.w < 0.0f ? 0.0f : v.w; }
             *reinterpret_cast<float4*>(a.out + (size_t)m * a.Cout + cb) = v;
         }
         return;
@@ -155,7 +155,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, float* smem, co
                     v += (((q[0] + q[a.XC]) + q[(size_t)a.XW * a.XC]) + q[(size_t)a.XW * a.XC + a.XC]) * 0.25f;
                 }
             }
-            if (a.relu && v < 0.0f) v = 0.0f;
+            if (v < 0.0f) v = 0.0f;
             a.out[(size_t)m * a.Cout + col] = v;
         }
 }
@@ -411,8 +411,11 @@ __global__ void __launch_bounds__(256) conv_split_k(ConvArgs a)
         for (int q = 0; q < A_F4; ++q) {
             const f32x4 xv = __builtin_bit_cast(f32x4, va[q]) * sa;       // (the whole vector: a bit_cast of one element read element 0)
             const float x0 = xv.x, x1 = xv.y, x2 = xv.z, x3 = xv.w;
-            const float mx = fmaxf(fmaxf(fabsf(x0), fabsf(x1)), fmaxf(fabsf(x2), fabsf(x3)));
-            bad |= (mx < EMB_F16_LIMIT) ? 0 : (1 << q);      // (NaN included; a row without a pixel loads zeros only)
+            // every value on its own: a NaN fails its comparison (fmaxf over the four would drop a NaN that stands next to a number, and
+            // the face would not be marked); a row without a pixel loads zeros only
+            const int ok = (int)(fabsf(x0) < EMB_F16_LIMIT) & (int)(fabsf(x1) < EMB_F16_LIMIT) & (int)(fabsf(x2) < EMB_F16_LIMIT) &
+                           (int)(fabsf(x3) < EMB_F16_LIMIT);
+            bad |= ok ? 0 : (1 << q);
             const _Float16 h0 = (_Float16)x0, h1 = (_Float16)x1, h2 = (_Float16)x2, h3 = (_Float16)x3;
             const f16x2 h01 = {h0, h1}, h23 = {h2, h3};
             const f16x2 l01 = {(_Float16)(x0 - (float)h0), (_Float16)(x1 - (float)h1)};
@@ -760,7 +763,7 @@ static void launch_conv(Ctx* c, const ConvArgs& a)
     PVF_REQUIRE(a.Cin % 32 == 0, "conv: input channels must be a multiple of 32 (the 3-channel first layer has a kernel of its own: stem_conv_k)");
     PVF_REQUIRE(a.OH * a.OW < (1 << 21) && a.Cout % 32 == 0, "conv: output map too large for the kernel's index arithmetic / Cout not a multiple of 32");
     if (a.frag && a.Cin == 32 && a.Cout == 32 && a.H == 35 && a.W == 35 && a.OH == 35 && a.OW == 35 && a.AH == 35 && a.AW == 35 && a.ksz == 3 &&
-        a.stride == 1 && a.pad == 1 && a.relu && a.skip_mode != 2) {
+        a.stride == 1 && a.pad == 1 && a.skip_mode != 2) {
         static std::atomic<uint64_t> attr_set{0};             // per device (a function attribute belongs to the device it was set on)
         const size_t lds = (size_t)(C32_TILE_FLOATS + 144 * 64) * sizeof(float);
         const uint64_t bit = 1ull << (c->device & 63);
@@ -781,6 +784,76 @@ static void launch_conv(Ctx* c, const ConvArgs& a)
         if (a.wsplit) hipLaunchKernelGGL((conv_split_k<2, 2>), grid, dim3(256), 0, c->stream, a);
         else hipLaunchKernelGGL((conv_mfma_k<2, 2>), grid, dim3(256), 0, c->stream, a);
     }
+}
+
+// ---- a layer's weights as the kernels read them (the model loader, resnet_run and pvf_debug_conv all come through here) -------------
+void conv_layer_upload(ConvLayer& L, const float* w, const float* bias, const float* gamma, const float* beta)
+{
+    const int cin = L.cin, cout = L.cout, k = L.k;
+    // [cout][cin][r][s] -> [cout][kk], kk = (r*k+s)*cp + c, rows zero-padded to a multiple of 32 (the conv kernel's K chunk); the
+    // 3-channel input layer is stored with a fourth, all-zero channel (cp = 4) so that the kernel stages one pixel tap with one 16-byte
+    // load: x + 0 * w is exact, the chain is unchanged
+    const int cp = (cin == 3) ? 4 : cin;
+    const int K = k * k * cp, Kpad = (K + 31) / 32 * 32;
+    std::vector<float> wt((size_t)cout * Kpad, 0.0f);
+    for (int o = 0; o < cout; ++o)
+        for (int ci = 0; ci < cin; ++ci)
+            for (int r = 0; r < k; ++r)
+                for (int s = 0; s < k; ++s) {
+                    const int kk = (r * k + s) * cp + ci;
+                    wt[(size_t)o * Kpad + kk] = w[(((size_t)o * cin + ci) * k + r) * k + s];
+                }
+    auto up = [](const float* src, size_t count) {
+        float* d = nullptr;
+        HIP_CHECK(hipMalloc((void**)&d, count * sizeof(float)));
+        HIP_CHECK(hipMemcpy(d, src, count * sizeof(float), hipMemcpyHostToDevice));
+        return d;
+    };
+    L.d_w = up(wt.data(), wt.size());
+    // the split path's weight scale: a power of two that puts the largest |w| in [2^14, 2^15) (a function of the weights only)
+    float wmax = 0.0f;
+    for (float v : wt) wmax = std::max(wmax, std::fabs(v));
+    int ex = 0;
+    if (wmax > 0.0f && std::isfinite(wmax)) { std::frexp(wmax, &ex); L.w_exp = 15 - ex; }     // wmax = f 2^ex, f in [0.5, 1)
+    L.d_bias = up(bias, cout);
+    L.d_gamma = up(gamma, cout);
+    L.d_beta = up(beta, cout);
+}
+
+void conv_layer_free(ConvLayer& L)
+{
+    for (void* p : {(void*)L.d_w, (void*)L.d_bias, (void*)L.d_gamma, (void*)L.d_beta, (void*)L.d_frag, (void*)L.d_wsplit})
+        if (p) (void)hipFree(p);
+    L.d_w = L.d_bias = L.d_gamma = L.d_beta = L.d_frag = nullptr;
+    L.d_wsplit = nullptr;
+}
+
+// the weight side of a's launch: d_w, and what the layer's kernel wants beside it, made on first use -- the fragment order for a
+// 32 -> 32 3 x 3 layer (conv3x3_c32_k; `generic`: not even there), else with `split` the f16 halves and their scale
+static void conv_bind_weights(Ctx* c, ConvLayer& L, bool split, bool generic, int* flags, ConvArgs& a)
+{
+    a.w = L.d_w; a.K = L.k * L.k * L.cin; a.bias = L.d_bias; a.gamma = L.d_gamma; a.beta = L.d_beta;
+    a.frag = nullptr; a.wsplit = nullptr; a.out_scale = 0.0f; a.flags = nullptr;
+    const bool own = !generic && L.cin == 32 && L.cout == 32 && L.k == 3;
+    if (own) {
+        if (!L.d_frag) {
+            HIP_CHECK(hipMalloc(&L.d_frag, 144 * 64 * sizeof(float)));
+            hipLaunchKernelGGL(conv_frag_k, dim3(144), dim3(64), 0, c->stream, L.d_w, 288, L.d_frag);
+        }
+        a.frag = L.d_frag;
+        return;                                         // (the 32-channel stage stays on conv3x3_c32_k)
+    }
+    if (!split) return;
+    if (!L.d_wsplit) {
+        const int Kpad = (L.k * L.k * L.cin + 31) / 32 * 32;
+        const int total = L.cout * Kpad;
+        HIP_CHECK(hipMalloc(&L.d_wsplit, (size_t)total * 2 * sizeof(_Float16)));
+        hipLaunchKernelGGL(conv_wsplit_k, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, L.d_w, total, L.w_exp,
+                           reinterpret_cast<_Float16*>(L.d_wsplit));
+    }
+    a.wsplit = L.d_wsplit;
+    a.out_scale = std::ldexp(1.0f, -(EMB_A_SCALE_EXP + L.w_exp));
+    a.flags = flags;
 }
 
 // ---- embed_probe: the f16 matrix pipe against what conv_split_k assumes (once per context, before the first split forward) ----------
@@ -861,7 +934,8 @@ static void embed_probe(Ctx* c)
 
 // d_chips: [n][150][150][3] u8 on device; h_out [n][128]; split: the convolutions outside the 32-channel stage on conv_split_k, and
 // h_flags[n] = 1 for the faces whose activations left its range
-static void resnet_run(Ctx* c, const uint8_t* d_chips, int n, float* h_out, bool split, int* h_flags)
+// tap (stage access, or null): the activation after tap->stage is copied to tap->h_out as well; launches, buffers and results are the same
+static void resnet_run(Ctx* c, const uint8_t* d_chips, int n, float* h_out, bool split, int* h_flags, const EmbedTap* tap = nullptr)
 {
     const EmbedModel& e = c->emb;
     PVF_REQUIRE(e.loaded, "embedder not loaded");
@@ -875,6 +949,11 @@ static void resnet_run(Ctx* c, const uint8_t* d_chips, int n, float* h_out, bool
     c->s_act0.ensure(std::max(big, (size_t)cap * S * S * 4) * sizeof(float));
     c->s_act1.ensure(big * sizeof(float));
     c->s_act2.ensure((size_t)cap * hp * hp * 32 * sizeof(float) + (size_t)cap * 128 * sizeof(float));
+    PVF_REQUIRE(!tap || n <= MAXB, "embedder stage access: at most 4096 faces");
+    auto tapped = [&](int stage, const float* d, int B, int H, int W, int C) {
+        if (tap && tap->stage == stage && tap->h_out)
+            HIP_CHECK(hipMemcpyAsync(tap->h_out, d, (size_t)B * H * W * C * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    };
     for (int b0 = 0; b0 < n; b0 += MAXB) {
         const int B = std::min(MAXB, n - b0);
         ProfScope ps(c, "conv");
@@ -890,69 +969,43 @@ static void resnet_run(Ctx* c, const uint8_t* d_chips, int n, float* h_out, bool
         }
         hipLaunchKernelGGL(stem_conv_k, dim3(h1 / STEM_ROWS, B), dim3(192), 0, c->stream, d_chips + (size_t)b0 * S * S * 3, B, c->emb.d_stem,
                            L0.d_bias, L0.d_gamma, L0.d_beta, y);
+        tapped(0, y, B, h1, h1, 32);
         ConvArgs a;
         const size_t npool = (size_t)B * hp * hp * 32;
         hipLaunchKernelGGL(maxpool3s2_k, dim3((unsigned)((npool + 255) / 256)), dim3(256), 0, c->stream, y, B, h1, h1, 32, z, hp, hp);
+        tapped(1, z, B, hp, hp, 32);
         // rotate buffers: cur = z (unit input), t1/t2 scratch
         float* cur = z; float* t1 = x; float* t2 = y;
         int H = hp, W = hp;
         static const int UN[14][3] = {{32, 32, 0}, {32, 32, 0}, {32, 32, 0}, {32, 64, 1}, {64, 64, 0}, {64, 64, 0}, {64, 64, 0},
                                       {64, 128, 1}, {128, 128, 0}, {128, 128, 0}, {128, 256, 1}, {256, 256, 0}, {256, 256, 0}, {256, 256, 1}};
-        // fragment-ordered weights of the 32 -> 32 layers, made on first use
-        auto frag_of = [&](int layer) -> const float* {
-            ConvLayer& L = c->emb.convs[layer];
-            if (L.cin != 32 || L.cout != 32 || L.k != 3) return nullptr;
-            if (!L.d_frag) {
-                HIP_CHECK(hipMalloc(&L.d_frag, 144 * 64 * sizeof(float)));
-                hipLaunchKernelGGL(conv_frag_k, dim3(144), dim3(64), 0, c->stream, L.d_w, 288, L.d_frag);
-            }
-            return L.d_frag;
-        };
-        // the split halves of the other layers' weights, made on first use
-        auto wsplit_of = [&](int layer) -> const uint32_t* {
-            ConvLayer& L = c->emb.convs[layer];
-            if (!split || (L.cin == 32 && L.cout == 32 && L.k == 3)) return nullptr;     // (the 32-channel stage stays on conv3x3_c32_k)
-            if (!L.d_wsplit) {
-                const int Kpad = (L.k * L.k * L.cin + 31) / 32 * 32;
-                const int total = L.cout * Kpad;
-                HIP_CHECK(hipMalloc(&L.d_wsplit, (size_t)total * 2 * sizeof(_Float16)));
-                hipLaunchKernelGGL(conv_wsplit_k, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, L.d_w, total, L.w_exp,
-                                   reinterpret_cast<_Float16*>(L.d_wsplit));
-            }
-            return L.d_wsplit;
-        };
         int* flags = nullptr;
         if (split) {
             flags = c->s_emb_flags.as<int>();
             HIP_CHECK(hipMemsetAsync(flags, 0, (size_t)B * sizeof(int), c->stream));
         }
-        auto set_split = [&](int layer) {
-            a.wsplit = wsplit_of(layer);
-            a.out_scale = std::ldexp(1.0f, -(EMB_A_SCALE_EXP + c->emb.convs[layer].w_exp));
-            a.flags = flags;
-        };
         for (int u = 0; u < 14; ++u) {
             const int cin = UN[u][0], nn = UN[u][1], down = UN[u][2];
-            const ConvLayer& La = e.convs[1 + 2 * u];
-            const ConvLayer& Lb = e.convs[2 + 2 * u];
+            ConvLayer& La = c->emb.convs[1 + 2 * u];
+            ConvLayer& Lb = c->emb.convs[2 + 2 * u];
             const int stride = down ? 2 : 1, pad = down ? 0 : 1;
             const int ah = 1 + (H + 2 * pad - 3) / stride, aw = 1 + (W + 2 * pad - 3) / stride;
             memset(&a, 0, sizeof a);
-            a.in = cur; a.B = B; a.H = H; a.W = W; a.Cin = cin; a.w = La.d_w; a.K = 9 * cin; a.bias = La.d_bias; a.gamma = La.d_gamma; a.beta = La.d_beta;
-            a.out = t1; a.OH = ah; a.OW = aw; a.Cout = nn; a.AH = ah; a.AW = aw; a.ksz = 3; a.stride = stride; a.pad = pad; a.relu = 1; a.skip_mode = 0;
-            a.frag = frag_of(1 + 2 * u);
-            set_split(1 + 2 * u);
+            a.in = cur; a.B = B; a.H = H; a.W = W; a.Cin = cin;
+            a.out = t1; a.OH = ah; a.OW = aw; a.Cout = nn; a.AH = ah; a.AW = aw; a.ksz = 3; a.stride = stride; a.pad = pad; a.skip_mode = 0;
+            conv_bind_weights(c, La, split, false, flags, a);
             launch_conv(c, a);
+            tapped(2 + 2 * u, t1, B, ah, aw, nn);
             int sh = H, sw = W;
             if (down) { sh = 1 + (H - 2) / 2; sw = 1 + (W - 2) / 2; }
             const int oh = std::max(ah, sh), ow = std::max(aw, sw);
             memset(&a, 0, sizeof a);
-            a.in = t1; a.B = B; a.H = ah; a.W = aw; a.Cin = nn; a.w = Lb.d_w; a.K = 9 * nn; a.bias = Lb.d_bias; a.gamma = Lb.d_gamma; a.beta = Lb.d_beta;
-            a.out = t2; a.OH = oh; a.OW = ow; a.Cout = nn; a.AH = ah; a.AW = aw; a.ksz = 3; a.stride = 1; a.pad = 1; a.relu = 1;
+            a.in = t1; a.B = B; a.H = ah; a.W = aw; a.Cin = nn;
+            a.out = t2; a.OH = oh; a.OW = ow; a.Cout = nn; a.AH = ah; a.AW = aw; a.ksz = 3; a.stride = 1; a.pad = 1;
             a.skip_mode = down ? 2 : 1; a.skip = cur; a.XH = H; a.XW = W; a.XC = cin; a.SH = sh; a.SW = sw;
-            a.frag = frag_of(2 + 2 * u);
-            set_split(2 + 2 * u);
+            conv_bind_weights(c, Lb, split, false, flags, a);
             launch_conv(c, a);
+            tapped(3 + 2 * u, t2, B, oh, ow, nn);
             float* old = cur; cur = t2; t2 = old;
             H = oh; W = ow;
         }
@@ -988,4 +1041,107 @@ void resnet_forward(Ctx* c, const uint8_t* d_chips, int n, float* h_out)
     std::vector<float> e(redo.size() * 128);
     resnet_run(c, d, (int)redo.size(), e.data(), false, nullptr);
     for (size_t j = 0; j < redo.size(); ++j) memcpy(h_out + (size_t)redo[j] * 128, e.data() + j * 128, 128 * sizeof(float));
+}
+
+// ---- stage access ---------------------------------------------------------------------------------
+// The forward as resnet_forward's first pass runs it, with one activation copied out (the faces a split run flags are reported, not
+// embedded again: the stages are the split kernels' own)
+void resnet_debug_stage(Ctx* c, const uint8_t* d_chips, int n, bool split, EmbedTap* tap, int* h_flags)
+{
+    PVF_REQUIRE(tap && tap->stage >= 0 && tap->stage < EMB_STAGES, "pvf_debug_embed_stage: stage must be 0..29");
+    {
+        // dims of every stage, as resnet_run walks them
+        int H = 72, C = 32;
+        if (tap->stage >= 1) H = 35;
+        for (int u = 0; 2 + 2 * u <= tap->stage; ++u) {
+            static const int UN[14][2] = {{32, 0}, {32, 0}, {32, 0}, {64, 1}, {64, 0}, {64, 0}, {64, 0}, {128, 1}, {128, 0}, {128, 0}, {256, 1}, {256, 0}, {256, 0}, {256, 1}};
+            C = UN[u][0];
+            const int a = UN[u][1] ? 1 + (H - 3) / 2 : H, s = UN[u][1] ? 1 + (H - 2) / 2 : H;
+            H = (tap->stage == 2 + 2 * u) ? a : std::max(a, s);
+        }
+        tap->dims[0] = H; tap->dims[1] = H; tap->dims[2] = C;
+    }
+    if (!tap->h_out) return;
+    if (split) c->s_emb_flags.ensure((size_t)std::min(n, 4096) * sizeof(int));
+    std::vector<float> desc((size_t)n * 128);
+    std::vector<int> flags(n, 0);
+    resnet_run(c, d_chips, n, desc.data(), split, flags.data(), tap);
+    if (h_flags) memcpy(h_flags, flags.data(), (size_t)n * sizeof(int));
+}
+
+namespace {
+struct Scoped {                                          // device memory of one debug call
+    void* p = nullptr;
+    explicit Scoped(size_t bytes) { HIP_CHECK(hipMalloc(&p, bytes ? bytes : 4)); }
+    ~Scoped() { if (p) (void)hipFree(p); }
+    Scoped(const Scoped&) = delete;
+    Scoped& operator=(const Scoped&) = delete;
+};
+struct ScopedLayer {
+    ConvLayer L{};
+    ~ScopedLayer() { conv_layer_free(L); }
+};
+}
+
+void resnet_debug_conv(Ctx* c, const int32_t* g, const float* in, const float* w, const float* bias, const float* gamma, const float* beta,
+                       const float* skip, bool split, bool force_generic, float* out, int32_t* flags)
+{
+    ConvArgs a;
+    memset(&a, 0, sizeof a);
+    a.B = g[0]; a.H = g[1]; a.W = g[2]; a.Cin = g[3]; a.OH = g[4]; a.OW = g[5]; a.Cout = g[6]; a.AH = g[7]; a.AW = g[8];
+    a.ksz = g[9]; a.stride = g[10]; a.pad = g[11]; a.skip_mode = g[12]; a.XH = g[13]; a.XW = g[14]; a.XC = g[15]; a.SH = g[16]; a.SW = g[17];
+    // what keeps every access of the kernels inside the tensors handed in (the shapes the launcher takes are launch_conv's business)
+    PVF_REQUIRE(in && w && bias && gamma && beta && out, "pvf_debug_conv: null tensor");
+    PVF_REQUIRE(a.B > 0 && a.H > 0 && a.W > 0 && a.Cin > 0 && a.OH > 0 && a.OW > 0 && a.Cout > 0 && a.ksz > 0 && a.ksz <= 7 && a.stride > 0 && a.pad >= 0,
+                "pvf_debug_conv: bad dimensions");
+    PVF_REQUIRE(a.AH > 0 && a.AW > 0 && a.AH <= a.OH && a.AW <= a.OW, "pvf_debug_conv: the convolution's extent must lie inside the output map");
+    PVF_REQUIRE(a.skip_mode >= 0 && a.skip_mode <= 2 && (a.skip_mode == 0 || skip), "pvf_debug_conv: skip_mode must be 0..2, with a skip tensor for 1 and 2");
+    const size_t n_in = (size_t)a.B * a.H * a.W * a.Cin, n_out = (size_t)a.B * a.OH * a.OW * a.Cout;
+    size_t n_skip = 0;
+    if (a.skip_mode == 1) n_skip = n_out;
+    if (a.skip_mode == 2) {
+        PVF_REQUIRE(a.XH > 0 && a.XW > 0 && a.XC > 0 && a.SH >= 0 && a.SW >= 0 && 2 * a.SH <= a.XH && 2 * a.SW <= a.XW,
+                    "pvf_debug_conv: the averaged skip map must lie inside the skip tensor");
+        n_skip = (size_t)a.B * a.XH * a.XW * a.XC;
+    }
+    PVF_REQUIRE(n_in < (1u << 30) && n_out < (1u << 30) && n_skip < (1u << 30), "pvf_debug_conv: tensor too large");
+    ScopedLayer sl;
+    sl.L.cin = a.Cin; sl.L.cout = a.Cout; sl.L.k = a.ksz; sl.L.stride = a.stride; sl.L.pad = a.pad;
+    conv_layer_upload(sl.L, w, bias, gamma, beta);
+    Scoped d_in(n_in * sizeof(float)), d_out(n_out * sizeof(float)), d_skip(n_skip * sizeof(float));
+    HIP_CHECK(hipMemcpyAsync(d_in.p, in, n_in * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (n_skip) HIP_CHECK(hipMemcpyAsync(d_skip.p, skip, n_skip * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_CHECK(hipMemsetAsync(d_out.p, 0xff, n_out * sizeof(float), c->stream));          // (NaN wherever the kernel does not write)
+    int* d_flags = nullptr;
+    if (split) {
+        c->s_emb_flags.ensure((size_t)a.B * sizeof(int));
+        d_flags = c->s_emb_flags.as<int>();
+        HIP_CHECK(hipMemsetAsync(d_flags, 0, (size_t)a.B * sizeof(int), c->stream));
+    }
+    a.in = reinterpret_cast<const float*>(d_in.p); a.out = reinterpret_cast<float*>(d_out.p);
+    a.skip = n_skip ? reinterpret_cast<const float*>(d_skip.p) : nullptr;
+    struct Drain { Ctx* c; ~Drain() { (void)hipStreamSynchronize(c->stream); } } drain{c};     // nothing of this call is in flight when its memory goes
+    conv_bind_weights(c, sl.L, split, force_generic, d_flags, a);
+    launch_conv(c, a);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(out, d_out.p, n_out * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (flags) {
+        if (a.flags) HIP_CHECK(hipMemcpyAsync(flags, d_flags, (size_t)a.B * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        else memset(flags, 0, (size_t)a.B * sizeof(int));
+    }
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+}
+
+void resnet_debug_head(Ctx* c, const float* x, int n, int hw, float* out)
+{
+    PVF_REQUIRE(c->emb.loaded, "embedder not loaded");
+    PVF_REQUIRE(x && out && n > 0 && hw > 0 && (size_t)n * hw < (1u << 22), "pvf_debug_embed_head: bad arguments");
+    const size_t n_x = (size_t)n * hw * 256;
+    Scoped d_x(n_x * sizeof(float)), d_o((size_t)n * 128 * sizeof(float));
+    struct Drain { Ctx* c; ~Drain() { (void)hipStreamSynchronize(c->stream); } } drain{c};
+    HIP_CHECK(hipMemcpyAsync(d_x.p, x, n_x * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(head_k, dim3(n), dim3(256), 0, c->stream, reinterpret_cast<const float*>(d_x.p), hw, c->emb.d_fc, reinterpret_cast<float*>(d_o.p));
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(out, d_o.p, (size_t)n * 128 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(hipStreamSynchronize(c->stream));
 }

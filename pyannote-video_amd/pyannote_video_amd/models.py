@@ -137,9 +137,12 @@ def resnet_param_layout():
     return lay
 
 
-def make_embedder(seed=20260926, fc_scale=None):
-    """Random-init weights with the architecture of dlib's face_recognition_model_v1 (29 conv layers)."""
+def make_embedder(seed=20260926, fc_scale=None, gamma_signs=False, beta_sigma=0.05):
+    """Random-init weights with the architecture of dlib's face_recognition_model_v1 (29 conv layers).
+    gamma_signs: every affine scale gets a random sign per channel (drawn from a stream of its own: the other values stay what the
+    seed gives without it); beta_sigma: the spread of the affine offsets."""
     rng = np.random.default_rng(seed)
+    sign_rng = np.random.default_rng([seed, 1])
     parts = []
     for name, shape in resnet_param_layout():
         kind = name.split(".")[-1]
@@ -152,8 +155,10 @@ def make_embedder(seed=20260926, fc_scale=None):
             a = rng.normal(0, 0.01, shape)
         elif kind == "g":
             a = (0.5 if ".b.g" in name else 1.0) + rng.normal(0, 0.05, shape)
+            if gamma_signs:
+                a = a * sign_rng.choice([-1.0, 1.0], shape)
         else:  # beta
-            a = rng.normal(0, 0.05, shape)
+            a = rng.normal(0, 0.05, shape) * (beta_sigma / 0.05)
         parts.append(a.astype(np.float32).reshape(-1))
     return {
         "emb.meta": np.array([150], np.int32),

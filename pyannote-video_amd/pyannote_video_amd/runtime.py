@@ -641,6 +641,62 @@ class Context(object):
         check(self._l.pvf_debug_extract_chip(self._h, f.handle, ptr(r), float(cs), float(sn), rows, cols, ptr(out)))
         return out
 
+    EMBED_STAGES = 30
+
+    def embed_stage(self, chips, stage, split):
+        """the embedder's activation after `stage` (0 first layer, 1 max-pool, 2 + 2u / 3 + 2u the `a` layer / the output of unit u),
+        float32 [n, H, W, C], and the per-face range flags of a split run (int32 [n]; zeros without split)"""
+        chips = np.ascontiguousarray(chips, np.uint8).reshape(-1, 150, 150, 3)
+        n = len(chips)
+        dims = np.zeros(3, np.int32)
+        check(self._l.pvf_debug_embed_stage(self._h, None, n, 1 if split else 0, int(stage), None, ptr(dims), None))
+        out = np.zeros((n,) + tuple(int(d) for d in dims), np.float32)
+        flags = np.zeros(n, np.int32)
+        check(self._l.pvf_debug_embed_stage(self._h, ptr(chips), n, 1 if split else 0, int(stage), ptr(out), ptr(dims), ptr(flags)))
+        return out, flags
+
+    def debug_conv(self, x, w, bias, gamma, beta, stride=1, pad=1, skip=None, skip_mode=0, out_hw=None, split=False, force_generic=False):
+        """one convolution layer through the embedder's launcher: x [B, H, W, Cin], w [Cout, Cin, k, k]; skip_mode 1: skip
+        [B, OH, OW, Cout]; 2: skip [B, XH, XW, XC], averaged 2 x 2 and zero-extended.  out_hw: the output map (default: the larger of
+        the convolution's and the averaged skip's).  Returns (float32 [B, OH, OW, Cout], flags int32 [B])."""
+        x = np.ascontiguousarray(x, np.float32)
+        w = np.ascontiguousarray(w, np.float32)
+        B, H, W, cin = x.shape
+        cout, wc, k, k2 = w.shape
+        if wc != cin or k != k2:
+            raise ValueError("debug_conv: weights do not fit the input")
+        ah, aw = 1 + (H + 2 * pad - k) // stride, 1 + (W + 2 * pad - k) // stride
+        xh = xw = xc = sh = sw = 0
+        if skip is not None:
+            skip = np.ascontiguousarray(skip, np.float32)
+        if skip_mode == 2:
+            _, xh, xw, xc = skip.shape
+            sh, sw = xh // 2, xw // 2
+        oh, ow = out_hw if out_hw is not None else (max(ah, sh), max(aw, sw))
+        if skip_mode == 1 and skip.shape != (B, oh, ow, cout):
+            raise ValueError("debug_conv: the skip tensor must have the output's shape")
+        if skip_mode == 2 and skip.shape[0] != B:
+            raise ValueError("debug_conv: one skip map per face")
+        par = [np.ascontiguousarray(v, np.float32).reshape(-1) for v in (bias, gamma, beta)]
+        if any(v.size != cout for v in par):
+            raise ValueError("debug_conv: bias, gamma and beta have one value per output channel")
+        geom = np.array([B, H, W, cin, oh, ow, cout, ah, aw, k, stride, pad, skip_mode, xh, xw, xc, sh, sw], np.int32)
+        out = np.zeros((B, max(oh, 0), max(ow, 0), cout), np.float32)
+        flags = np.zeros(B, np.int32)
+        check(self._l.pvf_debug_conv(self._h, ptr(geom), ptr(x), ptr(w), ptr(par[0]), ptr(par[1]), ptr(par[2]),
+                                     ptr(skip) if skip is not None else None, 1 if split else 0, 1 if force_generic else 0, ptr(out), ptr(flags)))
+        return out, flags
+
+    def embed_head(self, x):
+        """head_k (average over the map, 256 -> 128 product with the loaded model's matrix): x [n, HW, 256] -> float32 [n, 128]"""
+        x = np.ascontiguousarray(x, np.float32)
+        n, hw, ch = x.shape
+        if ch != 256:
+            raise ValueError("embed_head: 256 channels")
+        out = np.zeros((n, 128), np.float32)
+        check(self._l.pvf_debug_embed_head(self._h, ptr(x), n, hw, ptr(out)))
+        return out
+
     # ---- f4: shot boundary detection
     def shot_dfd(self, frames, width, height, tables, want_gray=False, want_flow=False):
         """displaced frame differences of consecutive frames (structure/shot.py:71-99): float64 [n - 1]
