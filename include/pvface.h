@@ -161,7 +161,12 @@ int32_t pvf_tracker_destroy_many(pvf_handle ctx, const pvf_handle* trks, int32_t
  * side writes them (start_track, a full update, the commit of a deferred update): only then is the 2.4 MB state copied. */
 int32_t pvf_tracker_clone_many(pvf_handle ctx, const pvf_handle* src, int32_t n, pvf_handle* dst);
 int32_t pvf_tracker_destroy(pvf_handle ctx, pvf_handle trk);
-/* ref: tracking.py:251  tracker.start_track(frame, dlib.drectangle(*detection)) ; box = (l,t,r,b) doubles */
+/* ref: tracking.py:251  tracker.start_track(frame, dlib.drectangle(*detection)) ; box = (l,t,r,b) doubles
+ * A box with a non-finite coordinate, or of exactly zero width or height, is refused with an error before any GPU work (its chip map
+ * would be 0/0); a refused pvf_tracker_start_many leaves EVERY tracker of the call as it was, and the context keeps working.  A box
+ * with r < l or b < t (dlib's empty rectangle) is accepted: it gives finite results like dlib's.  Boxes that cross or leave the
+ * frame are valid input: pixels outside the frame read as black.  On an all-black chip the response is all zero, the confidence
+ * that pvf_tracker_update returns is 0/0 = NaN, and NaN < threshold is false -- the reference keeps such a tracker, see DESIGN.md. */
 int32_t pvf_tracker_start(pvf_handle ctx, pvf_handle trk, pvf_handle frame, const double box[4]);
 /* ref: tracking.py:203  confidence = tracker.update(frame)   (peak-to-sidelobe ratio) */
 int32_t pvf_tracker_update(pvf_handle ctx, pvf_handle trk, pvf_handle frame, double* psr);
@@ -330,6 +335,8 @@ int32_t pvf_debug_detect_raw_many(pvf_handle ctx, const pvf_handle* frames, int3
 int32_t pvf_debug_extract_chip(pvf_handle ctx, pvf_handle frame, const double rect[4], double cs, double sn,
                                int32_t rows, int32_t cols, uint8_t* out);
 int32_t pvf_debug_tracker_state(pvf_handle ctx, pvf_handle trk, double* F, double* A, double* B);
+/* the scale filter of a started tracker: As [512][32][2] (index = (cell * 32 + plane), scale, re/im), Bs [32]; either may be NULL */
+int32_t pvf_debug_tracker_scale_state(pvf_handle ctx, pvf_handle trk, double* As, double* Bs);
 /* The embedder's forward as pvf_embed_chips runs it (split != 0: the f16 split path, without the exact second pass of flagged faces),
  * with the activation after `stage` copied out as out [n][dims[0]][dims[1]][dims[2]] fp32: stage 0 the first layer, 1 the max-pool,
  * 2 + 2u the `a` layer and 3 + 2u the output of residual unit u = 0..13 (30 stages; head_k, which averages and multiplies in one

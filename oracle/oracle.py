@@ -267,7 +267,10 @@ class Tracker(object):
 
     def start_track(self, rgb, box):
         rgb = _u8(rgb)
-        b = np.asarray(box, np.float64)
+        b = np.ascontiguousarray(box, np.float64).reshape(4)
+        # the boxes pvf_tracker_start_many refuses (include/pvface.h): their chip map is 0/0, and what follows is undefined in C
+        if not np.isfinite(b).all() or b[2] - b[0] == 0.0 or b[3] - b[1] == 0.0:
+            raise ValueError("start_track: box with a non-finite coordinate or of zero width or height: %r" % (tuple(b.tolist()),))
         lib().pvo_tracker_start(self._h, _p(rgb), rgb.shape[0], rgb.shape[1], _p(b))
 
     def update(self, rgb):
@@ -289,6 +292,20 @@ class Tracker(object):
         B = np.zeros((64, 64), np.float64)
         lib().pvo_tracker_debug_state(self._h, _p(A), _p(B))
         return A, B
+
+    def debug_scale_state(self):
+        As = np.zeros((512, 32, 2), np.float64)
+        Bs = np.zeros(32, np.float64)
+        lib().pvo_tracker_debug_scale_state(self._h, _p(As), _p(Bs))
+        return As, Bs
+
+    def debug_last(self):
+        """the last update's translation peak (ppx, ppy), its integer arg-max (ipx, ipy), how the sub-pixel step ended ('border': skipped,
+        'taken', 'det0', 'against': the two early returns), the scale arg-max bk and the interpolated scale position"""
+        d = np.zeros(8, np.float64)
+        lib().pvo_tracker_debug_last(self._h, _p(d))
+        return dict(ppx=d[0], ppy=d[1], ipx=int(d[2]), ipy=int(d[3]), how=("border", "taken", "det0", "against")[int(d[4])],
+                    bk=int(d[5]), spos=d[6])
 
 
 def fft64x64(data, tw64, inverse=False):

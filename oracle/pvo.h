@@ -139,6 +139,10 @@ void pvo_tracker_position(const pvo_tracker*, double box[4]);
 /* stage access for parity tests */
 void pvo_tracker_debug_F(const pvo_tracker*, double* out /* [32][64][64][2] */);
 void pvo_tracker_debug_state(const pvo_tracker*, double* A /*[32][64][64][2]*/, double* B /*[64][64]*/);
+void pvo_tracker_debug_scale_state(const pvo_tracker*, double* As /*[512][32][2]*/, double* Bs /*[32]*/);
+/* the last update's (ppx, ppy, integer peak x, y, interpolation outcome 0 border / 1 taken / 2 det == 0 / 3 against the gradient,
+ * scale arg-max bk, interpolated scale position, 0) */
+void pvo_tracker_debug_last(const pvo_tracker*, double out[8]);
 void pvo_fft64x64(double* data /* [64][64][2] in place */, const double* tw64, int inverse);
 double pvo_det_exp(double x);
 

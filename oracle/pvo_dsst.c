@@ -33,6 +33,7 @@ struct pvo_tracker {
     double* As;   /* [SDIM][NSC][2] */
     double Bs[NSC];
     double pos[4];
+    double dbg[8]; /* last update: ppx, ppy, integer peak x, y, interpolation outcome, bk, interpolated scale position, 0 */
 };
 
 double pvo_det_exp(double x)
@@ -210,6 +211,12 @@ void pvo_tracker_free(pvo_tracker* tk)
 }
 void pvo_tracker_position(const pvo_tracker* tk, double box[4]) { memcpy(box, tk->pos, sizeof(double) * 4); }
 void pvo_tracker_debug_F(const pvo_tracker* tk, double* out) { memcpy(out, tk->F, sizeof(double) * NPL * FS * FS * 2); }
+void pvo_tracker_debug_last(const pvo_tracker* tk, double out[8]) { memcpy(out, tk->dbg, sizeof tk->dbg); }
+void pvo_tracker_debug_scale_state(const pvo_tracker* tk, double* As, double* Bs)
+{
+    memcpy(As, tk->As, sizeof(double) * SDIM * NSC * 2);
+    memcpy(Bs, tk->Bs, sizeof(double) * NSC);
+}
 void pvo_tracker_debug_state(const pvo_tracker* tk, double* A, double* B)
 {
     memcpy(A, tk->A, sizeof(double) * NPL * FS * FS * 2);
@@ -255,14 +262,15 @@ void pvo_tracker_start(pvo_tracker* tk, const uint8_t* rgb, int h, int w, const 
 }
 
 /* [EXT max_point_interpolated]: least-squares quadratic surface on the 3x3 neighbourhood of the arg-max */
-static void peak_interp(const double* R, int n, int* ipx, int* ipy, double* ox, double* oy)
+/* returns how it ended: 0 = peak on the border (no interpolation), 1 = interpolated, 2 = det == 0, 3 = step against the gradient */
+static int peak_interp(const double* R, int n, int* ipx, int* ipy, double* ox, double* oy)
 {
     int bi = 0;
     double bv = R[0];
     for (int i = 1; i < n * n; ++i) if (R[i] > bv) { bv = R[i]; bi = i; }
     const int py = bi / n, px = bi % n;
     *ipx = px; *ipy = py; *ox = px; *oy = py;
-    if (px < 1 || py < 1 || px > n - 2 || py > n - 2) return;
+    if (px < 1 || py < 1 || px > n - 2 || py > n - 2) return 0;
     double z[3][3];
     for (int r = -1; r <= 1; ++r) for (int c = -1; c <= 1; ++c) z[r + 1][c + 1] = R[(py + r) * n + (px + c)];
     const double sx = ((z[0][2] + z[1][2]) + z[2][2]) - ((z[0][0] + z[1][0]) + z[2][0]);
@@ -275,15 +283,16 @@ static void peak_interp(const double* R, int n, int* ipx, int* ipy, double* ox, 
     const double k4 = sxx / 2.0 - sall / 3.0, k6 = syy / 2.0 - sall / 3.0;
     const double h00 = 2 * k4, h01 = k5, h11 = 2 * k6;
     const double det = h00 * h11 - h01 * h01;
-    if (det == 0) return;
+    if (det == 0) return 2;
     double dx = -((h11 * k2 - h01 * k3) / det);
     double dy = -((h00 * k3 - h01 * k2) / det);
-    if (dx * k2 + dy * k3 < 0) return;
+    if (dx * k2 + dy * k3 < 0) return 3;
     if (dx < -1) dx = -1;
     if (dx > 1) dx = 1;
     if (dy < -1) dy = -1;
     if (dy > 1) dy = 1;
     *ox = px + dx; *oy = py + dy;
+    return 1;
 }
 
 double pvo_tracker_update(pvo_tracker* tk, const uint8_t* rgb, int h, int w)
@@ -309,7 +318,8 @@ double pvo_tracker_update(pvo_tracker* tk, const uint8_t* rgb, int h, int w)
     for (int q = 0; q < FS * FS; ++q) R[q] = G[2 * q];
     int ipx, ipy;
     double ppx, ppy;
-    peak_interp(R, FS, &ipx, &ipy, &ppx, &ppy);
+    const int how = peak_interp(R, FS, &ipx, &ipy, &ppx, &ppy);
+    tk->dbg[0] = ppx; tk->dbg[1] = ppy; tk->dbg[2] = ipx; tk->dbg[3] = ipy; tk->dbg[4] = how;
     /* PSR: point p = pp (rounded); exclude centered_rect(p,8,8) = [p-4, p+3] */
     const long rx = (long)floor(ppx + 0.5), ry = (long)floor(ppy + 0.5);
     double sum = 0, sumsq = 0, cnt = 0;
@@ -385,6 +395,7 @@ double pvo_tracker_update(pvo_tracker* tk, const uint8_t* rgb, int h, int w)
             if (pos > p3) pos = p3;
         }
     }
+    tk->dbg[5] = bk; tk->dbg[6] = pos;
     scale_rect(tk->pos, pvo_det_exp((pos - (double)NSC / 2) * tk->tb.ln_alpha));
     scale_target(tk, pos, Gs);
     for (int k = 0; k < NSC; ++k) {

@@ -336,6 +336,16 @@ extern "C" int32_t pvf_tracker_start_many(pvf_handle h, const pvf_handle* trks, 
     ENTER(c, h);
     std::vector<Tracker*> t(n);
     std::vector<Frame> f(n);
+    PVF_REQUIRE(n >= 0 && (n == 0 || (trks && frames && boxes)), "tracker.start_track: bad arguments");
+    // a box with a non-finite coordinate or an extent of exactly zero has no chip (0/0 in its chip map): the whole call is refused
+    // before anything is touched, so every tracker of the call keeps the state and position it had (oracle.Tracker.start_track
+    // raises for the same boxes).  Negative extents (inverted boxes) are dlib's empty rectangles and stay accepted.
+    for (int i = 0; i < n; ++i) {
+        const double* b = boxes + 4 * (size_t)i;
+        PVF_REQUIRE(std::isfinite(b[0]) && std::isfinite(b[1]) && std::isfinite(b[2]) && std::isfinite(b[3]),
+                    "tracker.start_track: box with a non-finite coordinate");
+        PVF_REQUIRE(b[2] - b[0] != 0.0 && b[3] - b[1] != 0.0, "tracker.start_track: box of zero width or height");
+    }
     for (int i = 0; i < n; ++i) { t[i] = &c->tracker(trks[i]); f[i] = c->frame(frames[i]); }
     dsst_start_many(c, t, f, boxes);
     API_END
@@ -399,6 +409,18 @@ extern "C" int32_t pvf_debug_tracker_state(pvf_handle h, pvf_handle trk, double*
     if (F && c->s_trk1.p) HIP_CHECK(hipMemcpy(F, c->s_trk1.p, (size_t)32 * 64 * 64 * 2 * sizeof(double), hipMemcpyDeviceToHost));
     if (A) HIP_CHECK(hipMemcpy(A, t.d_state + TRK_A, (size_t)32 * 64 * 64 * 2 * sizeof(double), hipMemcpyDeviceToHost));
     if (B) HIP_CHECK(hipMemcpy(B, t.d_state + TRK_B, (size_t)64 * 64 * sizeof(double), hipMemcpyDeviceToHost));
+    API_END
+}
+
+extern "C" int32_t pvf_debug_tracker_scale_state(pvf_handle h, pvf_handle trk, double* As, double* Bs)
+{
+    API_BEGIN
+    ENTER(c, h);
+    Tracker& t = c->tracker(trk);
+    PVF_REQUIRE(t.d_state, "tracker has no state yet (start_track first)");
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+    if (As) HIP_CHECK(hipMemcpy(As, t.d_state + TRK_AS, (size_t)512 * 32 * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    if (Bs) HIP_CHECK(hipMemcpy(Bs, t.d_state + TRK_BS, (size_t)32 * sizeof(double), hipMemcpyDeviceToHost));
     API_END
 }
 

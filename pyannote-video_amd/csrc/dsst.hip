@@ -265,7 +265,7 @@ __device__ __forceinline__ void peak_body(double2* s, const TrkJob& j, int b, co
     __shared__ double pk[4];
     const int tid = threadIdx.x;
     fft2d_lds<NT>(s, tw64, true);
-    // arg-max of the real part, first occurrence in row-major order
+    // arg-max of the real part, first occurrence in row-major order (0x7fffffff: this thread met nothing above -inf)
     double bv = -INFINITY; int bi = 0x7fffffff;
     for (int q = tid; q < FS * FS; q += NT) {
         const double v = FFT_AT(s, q >> 6, q & 63).x;
@@ -281,7 +281,13 @@ __device__ __forceinline__ void peak_body(double2* s, const TrkJob& j, int b, co
         __syncthreads();
     }
     if (tid == 0) {
-        const int py = red_i[0] >> 6, px = red_i[0] & 63;
+        // the oracle's rule (peak_interp): start at index 0, then strict > in row-major order.  The search above equals it whenever
+        // something compares greater than -inf and element 0 is a number; a map of NaN / -inf only leaves the sentinel in red_i[0],
+        // and behind a NaN at index 0 nothing ever compares greater: both are index 0 there.
+        int best = red_i[0];
+        const double r00 = FFT_AT(s, 0, 0).x;
+        if (best == 0x7fffffff || r00 != r00) best = 0;
+        const int py = best >> 6, px = best & 63;
         double ox = px, oy = py;
         if (!(px < 1 || py < 1 || px > FS - 2 || py > FS - 2)) {
             double z[3][3];

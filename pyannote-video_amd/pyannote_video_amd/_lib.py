@@ -116,6 +116,7 @@ _SIGS = {
     "pvf_debug_detect_raw_many": (C.c_int32, [H, P, C.c_int32, C.c_int32, C.c_int32, C.c_double, P, P, C.c_int64, P]),
     "pvf_debug_extract_chip": (C.c_int32, [H, H, P, C.c_double, C.c_double, C.c_int32, C.c_int32, P]),
     "pvf_debug_tracker_state": (C.c_int32, [H, H, P, P, P]),
+    "pvf_debug_tracker_scale_state": (C.c_int32, [H, H, P, P]),
     "pvf_debug_embed_stage": (C.c_int32, [H, P, C.c_int32, C.c_int32, C.c_int32, P, P, P]),
     "pvf_debug_conv": (C.c_int32, [H, P, P, P, P, P, P, P, C.c_int32, C.c_int32, P, P]),
     "pvf_debug_embed_head": (C.c_int32, [H, P, C.c_int32, C.c_int32, P]),

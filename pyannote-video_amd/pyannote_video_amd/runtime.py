@@ -587,6 +587,12 @@ class Context(object):
         check(self._l.pvf_debug_tracker_state(self._h, trk, ptr(F), ptr(A), ptr(B)))
         return F, A, B
 
+    def tracker_scale_state(self, trk):
+        As = np.zeros((512, 32, 2), np.float64)
+        Bs = np.zeros(32, np.float64)
+        check(self._l.pvf_debug_tracker_scale_state(self._h, trk, ptr(As), ptr(Bs)))
+        return As, Bs
+
     # ---- S4
     def landmarks(self, frames, boxes):
         n = len(boxes)

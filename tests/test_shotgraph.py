@@ -13,7 +13,7 @@ from pyannote_video_amd.tracking_by_detection import TrackingByDetection, HipTra
 from test_host_logic import scenario, FakeTrackerContext, ModelScriptTracker, ModelRefTracker
 
 
-def _both(seed, n, faces, p_miss, p_false, ratio, gap, dup=False, every=1):
+def _both(seed, n, faces, p_miss, p_false, ratio, gap, dup=False, every=1, tracker=ModelScriptTracker):
     frames, dets = scenario(seed, n=n, faces=faces, p_miss=p_miss, p_false=p_false)
     if every > 1:
         dets = [d if i % every == 0 else [] for i, d in enumerate(dets)]
@@ -23,7 +23,7 @@ def _both(seed, n, faces, p_miss, p_false, ratio, gap, dup=False, every=1):
     cache = list(zip(times, frames))
     out = []
     for python_lanes in (False, True):
-        ctx = FakeTrackerContext(ModelScriptTracker)
+        ctx = FakeTrackerContext(tracker)
         backend = HipTrackers(ctx)
         tbd = TrackingByDetection(detect_func=None, track_min_overlap_ratio=ratio, track_max_gap=gap, trackers=backend)
         tbd.python_lanes = python_lanes
