@@ -322,6 +322,9 @@ int32_t pvf_debug_pyramid_batch(pvf_handle ctx, const pvf_handle* frames, int32_
 /* features of one pyramid level exactly as the batched detector computes them (all levels per launch); out [fh][fw][32] or NULL */
 int32_t pvf_debug_level_features(pvf_handle ctx, pvf_handle frame, int32_t upsample, int32_t level,
                                  float* out, int32_t* fh, int32_t* fw);
+/* how the plan of the frame's size cuts one level into pieces: out8 = level height, width, feature rows, feature columns, FHOG chunk
+   height (feature rows), FHOG chunks, scoring piece height (output rows), scoring pieces */
+int32_t pvf_debug_level_plan(pvf_handle ctx, pvf_handle frame, int32_t upsample, int32_t level, int32_t* out8);
 int32_t pvf_debug_fhog(pvf_handle ctx, const uint8_t* img, int32_t h, int32_t w, int32_t cell, int32_t pad_r,
                        int32_t pad_c, float* out, int32_t* fh, int32_t* fw);          /* out [fh][fw][32] */
 int32_t pvf_debug_detect_raw(pvf_handle ctx, pvf_handle frame, int32_t upsample, double adjust, float* scores,

@@ -236,6 +236,15 @@ extern "C" int32_t pvf_debug_level_features(pvf_handle h, pvf_handle frame, int3
     API_END
 }
 
+extern "C" int32_t pvf_debug_level_plan(pvf_handle h, pvf_handle frame, int32_t upsample, int32_t level, int32_t* out8)
+{
+    API_BEGIN
+    ENTER_DET(c, h);
+    PVF_REQUIRE(out8 != nullptr, "pvf_debug_level_plan: out8 is NULL");
+    det_level_plan(c, c->frame(frame), upsample, level, out8);
+    API_END
+}
+
 extern "C" int32_t pvf_debug_fhog(pvf_handle h, const uint8_t* img, int32_t ih, int32_t iw, int32_t cell, int32_t pad_r, int32_t pad_c,
                                   float* out, int32_t* fh, int32_t* fw)
 {

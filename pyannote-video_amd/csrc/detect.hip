@@ -71,9 +71,12 @@ __global__ void __launch_bounds__(256) resize_rows_k(const uint8_t* const* __res
     const int seg_bytes = min(ow - c0, 64) * 3;
     const bool stores = (4 * lane < seg_bytes);
     // the frame behind a buffer descriptor whose base is 4-byte aligned (`delta` = what the alignment cut off): a row's window starts at
-    // the aligned dword that holds the wave's first source byte; dwords past the frame's end read as zero
+    // the aligned dword that holds the wave's first source byte; dwords past the frame's end read as zero.  The length is rounded UP to
+    // whole dwords: a dword load that straddles the end of the range is out of range as a whole (observed on gfx950: with the exact
+    // length the last 1 .. 3 bytes of a frame whose end is not 4-byte aligned -- its bottom-right pixel -- read as zero), and the aligned
+    // dword that holds the frame's last byte lies in the page that byte lies in, whatever follows the frame in it is never used as a pixel
     const unsigned delta = (unsigned)((uintptr_t)in & 3u);
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)((uintptr_t)in - delta), 0, (int)(delta + (unsigned)ih * (unsigned)in_rb), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)((uintptr_t)in - delta), 0, (int)((delta + (unsigned)ih * (unsigned)in_rb + 3u) & ~3u), 0x00020000);
     const int lane4 = 4 * lane;
     // a wave writes NSTRIP strips of RS output rows, one below the other; the next strip's source rows are requested (into registers)
     // before the current strip's arithmetic starts and go to LDS when it is done: the wave's memory phase lies under its compute phase
@@ -1245,6 +1248,17 @@ void det_level_features(Ctx* c, const Frame& f, int upsample, int level, std::ve
                     memcpy(out->data() + ((size_t)y * d.fw + x) * PVF_FHOG_STRIDE + 4 * j, dev.data() + feat_at(y, j, x, d.fwp), 4 * sizeof(float));
     }
     HIP_CHECK(hipStreamSynchronize(c->det_stream));
+}
+
+// how the plan of a frame's size cuts one level into pieces (tests: PVF_FHOG_CHUNK / PVF_SCORE_SEG are read when the plan is built)
+void det_level_plan(Ctx* c, const Frame& f, int upsample, int level, int32_t out[8])
+{
+    PVF_REQUIRE(c->det.loaded, "detector not loaded");
+    MlPlan* p = ml_plan(c, f.h, f.w, upsample, 1);
+    PVF_REQUIRE(level >= 0 && level < (int)p->lv.size(), "pyramid level out of range");
+    const LvDesc& d = p->lv[level];
+    const int32_t v[8] = {d.h, d.w, d.hog_nr, d.hog_nc, d.chunk_rows, d.chunks, d.roll_rows, d.roll_nseg};
+    memcpy(out, v, sizeof v);
 }
 
 static bool raw_less(const RawDet& x, const RawDet& y)

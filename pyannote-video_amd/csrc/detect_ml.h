@@ -25,7 +25,8 @@ struct MlStarts { int nl; int b0[ML_MAX + 1]; };
 // 3.0 of the kernel's 7.8 ms per 125 frames, tools/probes/store_pattern_probe.hip: 3.65 against 5.7 TB/s for the same bytes).  The readers
 // fetch 16-byte pieces anyway (a slab of cells for the matrix cores); they address piece (row, j, column) instead of (row, column, j).
 // A stored row is FEAT_PAD_COLS columns longer than the map and those columns hold zeros (written with the zero border): the screening
-// pass reads up to 49 cells past the last column of a level's last strip and relies on finding zeros there.
+// pass reads up to 47 cells past the last column of a level's last strip (columns fw .. fw + 46: derived below, at SCR_TAIL_CELLS) and
+// relies on finding zeros there.
 #define FEAT_PAD_COLS 52
 __host__ __device__ __forceinline__ size_t feat_at(int row, int j, int col, int fwp) { return (((size_t)row * 8 + j) * fwp + col) * 4; }   // in floats
 
@@ -34,6 +35,14 @@ struct CandRec { float score; int32_t filter, level, r, c; };
 
 // ---- screen.hip: the f16 screening pass in front of the exact chain -------------------------------------------------------------
 #define SCR_SG 4                                // 16-base groups per column strip: a strip is SCR_SG * 48 output columns wide
+#define SCR_GROUP_COLS 48                       // output columns of a group: 16 bases x 3 cells
+#define SCR_TAIL_CELLS 9                        // cells the tail group reads behind a strip's last group: bases 16 NG .. 16 NG + 2, three cells each
+#define SCR_FILTER_COLS 10                      // filter columns: a level has out_c = fw - (SCR_FILTER_COLS - 1) output columns
+// The last cell a walk of ng groups reads is c_base + 48 ng + SCR_TAIL_CELLS - 1, and 48 ng <= out_c - c_base + 47: at most
+// out_c + 55 = fw + 46.  It has to lie inside the stored row of its plane group (fw + FEAT_PAD_COLS cells), whose cells past fw are
+// zeros: the next plane group's cells would be read as this one's otherwise.  screen_plan_build checks every item against it.
+static_assert((SCR_GROUP_COLS - 1) + SCR_TAIL_CELLS - (SCR_FILTER_COLS - 1) <= FEAT_PAD_COLS,
+              "FEAT_PAD_COLS: the screening pass's tail read leaves a feature row's zero columns");
 struct ScreenItem { int32_t lv, b, c_base, r_base, out_rows, ng; };      // one wave's walk: a strip of ng groups x out_rows output rows
 // counters behind the per-frame candidate counts of a batch (d_counts + B): zeroed with them, copied back with them
 enum { SCR_CURSOR = 0, SCR_FLAGGED = 1, SCR_VIOLATION = 2, SCR_CTL_INTS = 4 };

@@ -67,12 +67,13 @@ __device__ __forceinline__ void screen_walk(const ScreenItem t, const LvDesc* __
 {
     constexpr int RSRC_FLAGS = 0x00020000;
     constexpr int FR = 10, FC = 10;
+    static_assert(FC == SCR_FILTER_COLS, "detect_ml.h: SCR_FILTER_COLS is this kernel's filter width");
     const int lane = threadIdx.x & 63, i = lane & 15, kq = lane >> 4;
     const int fw = lv[t.lv].fw;
     const long long feat_off = lv[t.lv].feat_off, feat_stride = lv[t.lv].feat_stride;
     // feature maps are [row][plane group][column][4 planes] with FEAT_PAD_COLS zero columns behind every run (detect_ml.h: feat_at): a
     // lane's planes 8 kq .. 8 kq + 7 of a cell are the pieces of the plane groups 2 kq and 2 kq + 1, fwp * 16 bytes apart, and a cell
-    // past the level's last column (the last strip's overhang: < 48 + 3 cells) reads zeros
+    // past the level's last column (the last strip's overhang: at most 47 cells, columns fw .. fw + 46 -- detect_ml.h: SCR_TAIL_CELLS) reads zeros
     const int fwp = lv[t.lv].fwp;
     const float* fb = feat_base + feat_off + (size_t)t.b * feat_stride + feat_at(t.r_base, 0, t.c_base, fwp);
     const int row_bytes = (8 * fwp - t.c_base) * 16;
@@ -422,6 +423,10 @@ void screen_plan_build(ScreenPlan& sp, const std::vector<LvDesc>& lv, int B)
                 for (int b = 0; b < B; ++b)
                     items.push_back(ScreenItem{l, b, c0, r0, std::min(rows, out_r - r0), std::min(SCR_SG, (out_c - c0 + 47) / 48)});
     }
+    // every walk's last read cell (its tail group's) stays inside the stored feature row: behind fw there are FEAT_PAD_COLS zero columns
+    for (const ScreenItem& it : items)
+        PVF_REQUIRE(it.ng >= 1 && it.c_base + SCR_GROUP_COLS * it.ng + SCR_TAIL_CELLS - 1 < lv[it.lv].fwp,
+                    "screening plan: a strip's tail read passes the FEAT_PAD_COLS zero columns of its feature row");
     std::stable_sort(items.begin(), items.end(), [](const ScreenItem& a, const ScreenItem& b) { return a.ng * (a.out_rows + 9) > b.ng * (b.out_rows + 9); });
     if (sp.d_items) (void)hipFree(sp.d_items);
     sp.d_items = nullptr;

@@ -111,6 +111,7 @@ _SIGS = {
     "pvf_debug_pyramid_level": (C.c_int32, [H, H, C.c_int32, C.c_int32, P, P, P]),
     "pvf_debug_pyramid_batch": (C.c_int32, [H, P, C.c_int32, C.c_int32]),
     "pvf_debug_level_features": (C.c_int32, [H, H, C.c_int32, C.c_int32, P, P, P]),
+    "pvf_debug_level_plan": (C.c_int32, [H, H, C.c_int32, C.c_int32, P]),
     "pvf_debug_fhog": (C.c_int32, [H, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P, P, P]),
     "pvf_debug_detect_raw": (C.c_int32, [H, H, C.c_int32, C.c_double, P, P, C.c_int32, P]),
     "pvf_debug_detect_raw_many": (C.c_int32, [H, P, C.c_int32, C.c_int32, C.c_int32, C.c_double, P, P, C.c_int64, P]),

@@ -514,6 +514,13 @@ class Context(object):
             check(self._l.pvf_debug_level_features(self._h, f.handle, upsample, level, ptr(out), C.byref(fh), C.byref(fw)))
         return out
 
+    def level_plan(self, frame, upsample, level):
+        """how the plan of the frame's size cuts one pyramid level into pieces (tests of the plan knobs)"""
+        f = self.stage(frame)
+        out = np.zeros(8, np.int32)
+        check(self._l.pvf_debug_level_plan(self._h, f.handle, int(upsample), int(level), ptr(out)))
+        return dict(zip(("h", "w", "hog_nr", "hog_nc", "chunk_rows", "chunks", "roll_rows", "roll_nseg"), (int(v) for v in out)))
+
     def fhog(self, img, cell, pad_r, pad_c):
         img = np.ascontiguousarray(img, np.uint8)
         fh, fw = C.c_int32(0), C.c_int32(0)
