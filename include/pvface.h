@@ -110,6 +110,46 @@ int32_t pvf_frame_from_yuv(pvf_handle ctx, const uint8_t* y, int64_t y_pitch, co
  * OpenCV's 8-bit INTER_LINEAR on the device; the source frame stays resident for `extract` */
 int32_t pvf_frame_resize(pvf_handle ctx, pvf_handle frame, int32_t out_w, int32_t out_h, pvf_handle* out);
 
+/* ---- annotated video out: the `demo` verb (DEMO.md) ------------------------------------------------- */
+/* ref: scripts/pyannote-face.py:317-384 (get_make_frame: cv2.resize through video.frame_size, cv2.putText / rectangle / line per face)
+ * and :401-413 (moviepy pushes RGB frames to ffmpeg).  One kernel per call resizes the resident frame (the bytes of pvf_frame_resize),
+ * draws the frame's primitives in list order (later ones overwrite earlier ones, each clipped to the frame) and converts to planar
+ * YUV 4:2:0: Y (out_h x out_w), then U, then V (ceil(out_h / 2) x ceil(out_w / 2) each), tight -- the layout pvf_ingest_create_yuv
+ * reads.  Integer arithmetic throughout; DEMO.md states it.  flags: PVF_YUV_BT709 / PVF_YUV_FULL_RANGE.
+ * A primitive is eight int32: rectangle outline (a, b, c, d) = (left, top, right, bottom), two pixels wide; line (a, b) - (c, d), one
+ * pixel wide; text with (a, b) the bottom-left corner of the first glyph's 5 x 7 box, c and d the offset and length of its bytes in
+ * the call's text pool, `scale` the side of a font pixel.  Coordinates are any int32.  colour = r | g << 8 | b << 16. */
+#define PVF_PRIM_RECT 0
+#define PVF_PRIM_LINE 1
+#define PVF_PRIM_TEXT 2
+#define PVF_RENDER_MAX_PRIMS 4096       /* primitives per frame */
+#define PVF_RENDER_MAX_RUN 64           /* bytes per text primitive */
+#define PVF_RENDER_MAX_TEXT (1 << 20)   /* text bytes per call */
+#define PVF_RENDER_MAX_SCALE 64
+#define PVF_RENDER_MAX_BATCH 1024       /* frames per pvf_render_batch call */
+typedef struct { int32_t type, a, b, c, d; uint32_t colour; int32_t scale, reserved; } pvf_prim;
+/* n resident frames of one size into `out` (n planar frames, tight; host memory, or device memory with out_on_device = 1); frame i
+ * draws prims[start[i] .. start[i + 1]) (start == NULL: nothing is drawn).  Complete when the call returns.  Refused with an error:
+ * an unknown or released frame, an output below 2 x 2, a list or a text pool beyond the caps above, a text run outside the pool. */
+int32_t pvf_render_batch(pvf_handle ctx, const pvf_handle* frames, int32_t n, int32_t out_w, int32_t out_h, int32_t flags,
+                         const int32_t* start, const pvf_prim* prims, const uint8_t* text, int64_t text_bytes,
+                         uint8_t* out, int32_t out_on_device);
+/* the egress ring, the mirror image of pvf_ingest_*: `depth` pinned host slots of one planar output frame.  pvf_egress_submit renders
+ * one frame into the next slot in ring order -- the kernel on the context's main stream, the device-to-host copy behind it on the ring's
+ * own copy stream -- and returns at once; pvf_egress_wait blocks until that slot's planes are in host memory and hands them out;
+ * pvf_egress_release gives the slot back.  Submit refuses (it does not wait) when the next slot has not been given back.  Rendering
+ * frame k + 1 overlaps the copy of frame k and whatever the host does with frame k - 1; wait / release may come from another thread.
+ * The source frame may be released as soon as submit has returned (pvf_frame_release: no wait on the GPU). */
+int32_t pvf_egress_create(pvf_handle ctx, int32_t out_w, int32_t out_h, int32_t depth, int32_t flags, pvf_handle* ring);
+int32_t pvf_egress_destroy(pvf_handle ctx, pvf_handle ring);
+int32_t pvf_egress_submit(pvf_handle ctx, pvf_handle ring, pvf_handle frame, const pvf_prim* prims, int32_t n_prims,
+                          const uint8_t* text, int64_t text_bytes, int32_t* slot);
+int32_t pvf_egress_wait(pvf_handle ctx, pvf_handle ring, int32_t slot, const uint8_t** host_planes);
+int32_t pvf_egress_release(pvf_handle ctx, pvf_handle ring, int32_t slot);
+/* the drawn picture BEFORE colour conversion, uint8 RGB [out_h][out_w][3] to host memory: tells resize, drawing and conversion apart */
+int32_t pvf_debug_render_rgb(pvf_handle ctx, pvf_handle frame, int32_t out_w, int32_t out_h, const pvf_prim* prims, int32_t n_prims,
+                             const uint8_t* text, int64_t text_bytes, uint8_t* rgb);
+
 /* ---- S1 detector ---------------------------------------------------------------------------------- */
 /* ref: face.py:64-67  for face in self.face_detector_(rgb, 1)  -> dlib.rectangle list, NMS order.
  * scores (optional) receive dlib's detection_confidence (score - threshold). */

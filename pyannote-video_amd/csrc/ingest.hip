@@ -407,8 +407,7 @@ extern "C" int32_t pvf_frame_from_yuv(pvf_handle h, const uint8_t* y, int64_t y_
 // (cvRound(f * 2048) as int16), horizontal pass in int32, vertical pass
 //   dst = (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2
 // The coefficient tables are built on the host (a few thousand entries), one lane = one output pixel (3 channels).
-struct ResizeTab { std::vector<int32_t> idx; std::vector<int16_t> coef; };
-static ResizeTab linear_table(int in, int out)
+ResizeTab linear_table(int in, int out)
 {
     ResizeTab t;
     t.idx.resize(out); t.coef.resize((size_t)out * 2);

@@ -273,6 +273,7 @@ struct Ctx {
     std::map<size_t, std::deque<PoolBuf>> frame_pool;      // oldest release first: its event is the most likely to have passed
     size_t frame_pool_bytes = 0;
     void* ingest_rings = nullptr;                          // pinned staging rings of this context (ingest.hip)
+    void* render_state = nullptr;                          // what the demo renderer keeps per context (render.hip)
     struct MlPlanCache* ml_plans = nullptr;   // detector launch plans of this context (detect.hip); freed by ml_plans_free
     std::map<std::vector<int>, std::unique_ptr<DevBuf>> resize_tabs;   // pvf_frame_resize coefficient tables by (in_w, in_h, out_w, out_h)
     const void* feat_ring_owner = nullptr;    // plan whose zero padding ring s_feat currently holds
@@ -366,6 +367,10 @@ void det_run_many(Ctx* c, const std::vector<Frame>& frames, int batch, int upsam
                   std::vector<std::vector<RawDet>>& raw_sorted, bool nms = false);
 void ml_plans_free(Ctx* c);
 void ingest_free_all(Ctx* c);
+// OpenCV's 8-bit INTER_LINEAR tables of one axis (ingest.hip): source index and the two 11-bit coefficients per output sample
+struct ResizeTab { std::vector<int32_t> idx; std::vector<int16_t> coef; };
+ResizeTab linear_table(int in, int out);
+void render_free_all(Ctx* c);            // render.hip: resize tables, scratch and egress rings of the context
 void det_nms(const DetectorModel& m, const std::vector<RawDet>& sorted, std::vector<RawDet>& out);
 void det_pyramid_level(Ctx* c, const Frame& f, int upsample, int level, std::vector<uint8_t>* out, int* h, int* w);
 void det_level_features(Ctx* c, const Frame& f, int upsample, int level, std::vector<float>* out, int* fh, int* fw);

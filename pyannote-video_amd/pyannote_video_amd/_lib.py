@@ -57,6 +57,13 @@ _SIGS = {
     "pvf_ingest_create_yuv": (C.c_int32, [H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P]),
     "pvf_frame_from_yuv": (C.c_int32, [H, P, C.c_int64, P, P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P]),
     "pvf_frame_resize": (C.c_int32, [H, H, C.c_int32, C.c_int32, P]),
+    "pvf_render_batch": (C.c_int32, [H, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P, P, P, C.c_int64, P, C.c_int32]),
+    "pvf_egress_create": (C.c_int32, [H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P]),
+    "pvf_egress_destroy": (C.c_int32, [H, H]),
+    "pvf_egress_submit": (C.c_int32, [H, H, H, P, C.c_int32, P, C.c_int64, P]),
+    "pvf_egress_wait": (C.c_int32, [H, H, C.c_int32, P]),
+    "pvf_egress_release": (C.c_int32, [H, H, C.c_int32]),
+    "pvf_debug_render_rgb": (C.c_int32, [H, H, C.c_int32, C.c_int32, P, C.c_int32, P, C.c_int64, P]),
     "pvf_detect": (C.c_int32, [H, H, C.c_int32, C.c_double, P, P, C.c_int32, P]),
     "pvf_detect_batch": (C.c_int32, [H, P, C.c_int32, C.c_int32, C.c_double, P, P, P, C.c_int32]),
     "pvf_detect_many": (C.c_int32, [H, P, C.c_int32, C.c_int32, C.c_int32, C.c_double, P, P, P, C.c_int32]),

@@ -6,11 +6,15 @@
     python -m pyannote_video_amd process [options] <video> <shot.json> <landmark_model> <embedding_model> <tracking> <landmarks> <embeddings>
     python -m pyannote_video_amd shot    [options] <video> <output.json>
     python -m pyannote_video_amd thread  [--min-match 20] [--lookahead 24] <video> <shot.json> <output.json>
+    python -m pyannote_video_amd demo    [--height 400] [--from 0] [--until T] [--shift 0] [--landmark PATH] [--label PATH] <video> <tracking> <output>
 
 `track` and `extract` take the reference's arguments and options and write byte-compatible files (track.txt, landmarks.txt,
 embedding.txt: formats.py).  `cluster` is the verb BASELINE.json's north_star names; the reference offers clustering through the API
 only (face/clustering.py:130-134).  It writes `identifier label` lines, the file `demo --label` reads (pyannote-face.py:87,391-397).
-`demo` (video rendering through moviepy) is out of scope.
+`demo` (pyannote-face.py:317-413) writes the video with the tracks, their numbers and labels and, with --landmark, the nose lines drawn
+on it, as a YUV4MPEG2 stream: to a `.y4m` path, or to stdout for `-` (`... demo film.y4m track.txt - | ffmpeg -i - out.mp4`).  Resize,
+drawing and RGB -> YUV 4:2:0 run in one kernel on the GPU (DEMO.md states every pixel; the font is the project's own, not OpenCV's
+Hershey).  Audio is not carried: the reference hands the source's audio track to moviepy, a Y4M stream has none.
 
 <video>: no codec is linked (reference video.py:345-406 runs ffmpeg); the verbs read what a decoder writes --
   * a YUV4MPEG2 file (`.y4m`, or any file that starts with `YUV4MPEG2`): 8-bit 4:2:0 / 4:2:2 / 4:4:4, memory mapped, frame rate from
@@ -314,7 +318,109 @@ def thread(video, shot, output, min_match=20, lookahead=24, ctx=None):
     return threads
 
 
-def main(argv=None):
+def demo(video, tracking, output, height=400, t_from=0.0, t_until=None, shift=0.0, landmark=None, label=None, matrix="601",
+         full_range=False, fps=None, ctx=None, ring_depth=16):
+    """Annotated video (pyannote-face.py:317-413) as YUV4MPEG2, to a path or to stdout (`-`).  What is drawn on which frame is planned
+    on the host (render.build_plan: the pacing of getFaceGenerator / getLandmarkGenerator); a reader thread pushes the frames the plan
+    shows through the pinned ingest ring (RGB or YUV, as `track` does), this thread submits one render per output frame to the egress
+    ring, a writer thread waits for the slots and writes them: rendering frame k + 1 overlaps the copy of frame k and the write of
+    frame k - 1.  Audio is not carried.  Returns {"frames": output frames, "width", "height"}."""
+    import queue
+    import threading
+    from . import render, runtime
+    ctx = ctx or runtime.default_context()
+    vw, vh = video.size
+    width, height = render.demo_size(vw, vh, height)
+    rate = float(video.frame_rate)
+    labels = render.read_labels(label) if isinstance(label, str) else label
+    marks = formats.read_landmarks(landmark) if isinstance(landmark, str) else landmark
+    rows = formats.read_tracks(tracking) if isinstance(tracking, str) else tracking
+    plan = render.build_plan(rows, rate, len(video), width, height, marks, labels, t_from, t_until, shift)
+    by_index = {}
+    for k, (i, _, _) in enumerate(plan):
+        by_index.setdefault(i, []).append(k)
+    last_wanted = max(by_index) if by_index else -1
+    ring = ctx.egress_ring(width, height, matrix, full_range, depth=ring_depth)
+    writer = render.Y4mWriter(output, width, height, render.rate_tag(video, fps if fps is not None else rate), full_range)
+    q = queue.Queue(maxsize=max(2, ring_depth))
+    wq = queue.Queue()
+    free = threading.Semaphore(ring_depth)             # slots the writer has given back
+    state = {"error": None}
+
+    def reader():
+        stager = runtime.HostFrameStager(ctx, ring_depth)
+        try:
+            if hasattr(video, "frame"):          # a source that can seek: only the frames the plan shows are read (--from deep into a file)
+                source = ((fi, video.frame(fi)) for fi in sorted(by_index))
+            else:
+                source = ((fi, frame) for fi, (_, frame) in enumerate(video) if fi in by_index or fi > last_wanted)
+            for fi, frame in source:
+                if fi > last_wanted or state["error"] is not None:
+                    break
+                q.put((fi,) + stager.stage(frame))
+            stager.close()
+        except BaseException as e:          # noqa: BLE001 -- re-raised below
+            state["error"] = e
+        finally:
+            q.put(None)
+
+    def drain():
+        try:
+            while True:
+                slot = wq.get()
+                if slot is None:
+                    return
+                if state["error"] is None:
+                    writer.write(ring.wait(slot))
+                    ring.release(slot)
+                free.release()
+        except BaseException as e:          # noqa: BLE001 -- re-raised below
+            state["error"] = e
+            free.release()
+            while wq.get() is not None:
+                free.release()
+
+    rt = threading.Thread(target=reader, name="pvface-demo-reader")
+    wt = threading.Thread(target=drain, name="pvface-demo-writer")
+    rt.start()
+    wt.start()
+    try:
+        while state["error"] is None:
+            item = q.get()
+            if item is None:
+                break
+            fi, dev, owned = item
+            for k in by_index[fi]:
+                free.acquire()
+                if state["error"] is not None:
+                    free.release()
+                    break
+                wq.put(ring.submit(dev, plan[k][2]))
+            if owned:
+                dev.release()                # the kernels that read it are queued: the buffer is recycled behind them
+    except BaseException as e:              # noqa: BLE001 -- re-raised below
+        state["error"] = state["error"] or e
+    finally:
+        wq.put(None)
+        wt.join()
+        while True:                          # an error on this side: let the reader run out, and release what it had staged
+            try:
+                left = q.get(timeout=0.05)
+            except queue.Empty:
+                if not rt.is_alive():
+                    break
+                continue
+            if left is not None and left[2]:
+                left[1].release()
+        rt.join()
+        writer.close()
+        ring.close()
+    if state["error"] is not None:
+        raise state["error"]
+    return {"frames": writer.frames, "width": width, "height": height}
+
+
+def _parser():
     ap = argparse.ArgumentParser(prog="pyannote-face", description="face tracking => feature extraction => face clustering (MI355X)")
     ap.add_argument("--fps", type=float, default=25.0, help="frame rate of a .npy / synthetic video (Y4M: only if its header names none)")
     ap.add_argument("--matrix", choices=("601", "709"), default=None, help="YUV matrix of a Y4M video (its header cannot name one; default BT.601)")
@@ -359,6 +465,23 @@ def main(argv=None):
     c.add_argument("--threshold", type=float, default=0.6)
     c.add_argument("--force", action="store_true")
     c.add_argument("--metric", choices=("euclidean", "cosine"), default="euclidean")
+    d = sub.add_parser("demo", help="the video with tracks, labels and landmarks drawn on it, as YUV4MPEG2")
+    d.add_argument("video"); d.add_argument("tracking"); d.add_argument("output", help="a .y4m path, or - for stdout")
+    d.add_argument("--height", type=int, default=400, help="height of the output frames; the width keeps the aspect")
+    d.add_argument("--from", dest="t_from", type=float, default=0.0, help="start, seconds")
+    d.add_argument("--until", dest="t_until", type=float, default=None, help="end, seconds (default: the video's duration)")
+    d.add_argument("--shift", type=float, default=0.0, help="shift the tracks by this many seconds")
+    d.add_argument("--landmark", default=None, help="landmarks.txt of `extract`: draws the nose line")
+    d.add_argument("--label", default=None, help="`identifier label` lines, what `cluster` writes")
+    return ap
+
+
+def parse_args(argv=None):
+    return _parser().parse_args(argv)
+
+
+def main(argv=None):
+    ap = _parser()
     a = ap.parse_args(argv)
     import time
     ctx = None
@@ -388,6 +511,11 @@ def main(argv=None):
         shot(video(), a.output, height=a.height, window=a.window, threshold=a.threshold, ctx=ctx)
     elif a.verb == "thread":
         thread(video(), a.shot, a.output, min_match=a.min_match, lookahead=a.lookahead, ctx=ctx)
+    elif a.verb == "demo":
+        v = video()
+        res = demo(v, a.tracking, a.output, height=a.height, t_from=a.t_from, t_until=a.t_until, shift=a.shift, landmark=a.landmark,
+                   label=a.label, matrix=a.matrix or getattr(v, "matrix", "601"),
+                   full_range=(a.range == "full") if a.range is not None else bool(getattr(v, "full_range", False)), fps=a.fps, ctx=ctx)
     elif a.verb == "extract":
         extract(video(), a.landmark_model, a.embedding_model, a.tracking, a.landmarks, a.embeddings, ctx=ctx)
     else:

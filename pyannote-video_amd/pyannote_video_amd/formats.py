@@ -70,6 +70,19 @@ def read_tracks(path):
     return [rows[i] for i in pandas_sort_order([r[0] for r in rows])]
 
 
+def read_landmarks(path):
+    """[(T, identifier, float32 [n, 2] normalised points)] in FILE order, as getLandmarkGenerator walks landmarks.txt (:184-207): the
+    values are parsed as float64 and narrowed to float32"""
+    rows = []
+    with open(path) as f:
+        for line in f:
+            p = line.split()
+            if not p:
+                continue
+            rows.append((float(p[0]), int(float(p[1])), np.array([float(v) for v in p[2:]], np.float64).astype(np.float32).reshape(-1, 2)))
+    return rows
+
+
 def _row_key(T, identifier):
     """one integer per (3-decimal time, track): a track has at most one row per timestamp"""
     return np.rint(np.asarray(T, np.float64) * 1000.0).astype(np.int64) * (1 << 24) + np.asarray(identifier, np.int64)

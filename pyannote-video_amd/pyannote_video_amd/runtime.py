@@ -131,6 +131,50 @@ class YuvIngestRing(IngestRing):
         return self.submit()
 
 
+class EgressRing(object):
+    """Pinned host slots of one planar YUV 4:2:0 output frame + a copy stream (pvf_egress_*): the way annotated frames leave the GPU,
+    the mirror image of IngestRing.  `submit(frame, prims)` renders the next slot (resize, drawing and colour conversion in one kernel on
+    the context's stream, the copy to the host queued behind it) and returns its number at once; `wait(slot)` blocks until the planes
+    are in host memory and returns them as a numpy view; `release(slot)` gives the slot back.  At most `depth` frames are in flight:
+    submit raises when the next slot has not been given back.  wait / release may run in another thread than submit."""
+
+    def __init__(self, ctx, width, height, matrix="601", full_range=False, depth=8):
+        self.ctx, self.w, self.h, self.depth = ctx, int(width), int(height), int(depth)
+        self.matrix, self.full_range = str(matrix), bool(full_range)
+        self._r = None
+        r = C.c_uint64(0)
+        check(ctx._l.pvf_egress_create(ctx._h, self.w, self.h, self.depth, _yuv_flags(matrix, full_range), C.byref(r)))
+        self._r = r.value
+        self.frame_bytes = self.w * self.h + 2 * ((self.w + 1) // 2) * ((self.h + 1) // 2)
+
+    def submit(self, frame, prims=()):
+        """frame: a DeviceFrame (or anything Context.stage takes); prims: one frame's primitive list (render.py)"""
+        from . import render as _render
+        _, p, text = _render.pack_primitives([prims])
+        s = C.c_int32(0)
+        check(self.ctx._l.pvf_egress_submit(self.ctx._h, self._r, self.ctx.stage(frame).handle, ptr(p), len(p), ptr(text), len(text), C.byref(s)))
+        return s.value
+
+    def wait(self, slot):
+        p = C.c_void_p(0)
+        check(self.ctx._l.pvf_egress_wait(self.ctx._h, self._r, int(slot), C.byref(p)))
+        return np.frombuffer((C.c_uint8 * self.frame_bytes).from_address(p.value), np.uint8)
+
+    def release(self, slot):
+        check(self.ctx._l.pvf_egress_release(self.ctx._h, self._r, int(slot)))
+
+    def close(self):
+        if self._r is not None and self.ctx._h is not None:
+            self.ctx._l.pvf_egress_destroy(self.ctx._h, self._r)
+        self._r = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class HostFrameStager(object):
     """What a reader thread does with the frames a video yields: numpy RGB frames go through a pinned RGB ring, YuvFrames through a YUV
     ring (made when the first such frame arrives, remade when the geometry changes); anything else -- a DeviceFrame -- is passed on
@@ -347,6 +391,42 @@ class Context(object):
 
     def ingest_ring_yuv(self, height, width, layout="420", matrix="601", full_range=False, depth=8):
         return YuvIngestRing(self, height, width, layout, matrix, full_range, depth)
+
+    def egress_ring(self, width, height, matrix="601", full_range=False, depth=8):
+        return EgressRing(self, width, height, matrix, full_range, depth)
+
+    def render(self, frames, prims, width, height, matrix="601", full_range=False, out_ptr=None):
+        """the `demo` picture of n resident frames of one size (pvf_render_batch): resized to (width, height), frame i drawn over with
+        prims[i] (render.py primitive lists; None: nothing is drawn), converted to planar YUV 4:2:0.  Returns uint8 [n, frame bytes]
+        (Y, U, V tight per frame); with out_ptr, a device address that holds as much, the planes stay in HBM and nothing is returned.
+        prims may also be the packed (start, prims, text) arrays of render.pack_primitives."""
+        from . import render as _render
+        n = len(frames)
+        if prims is None:
+            start, p, text = None, None, np.zeros(0, np.uint8)
+        elif isinstance(prims, tuple) and len(prims) == 3 and isinstance(prims[0], np.ndarray):
+            start, p, text = prims
+        else:
+            if len(prims) != n:
+                raise ValueError("%d primitive lists for %d frames" % (len(prims), n))
+            start, p, text = _render.pack_primitives(prims)
+        fb = int(width) * int(height) + 2 * ((int(width) + 1) // 2) * ((int(height) + 1) // 2)
+        out = None if out_ptr is not None else np.empty((n, fb), np.uint8)
+        with self._staging():
+            hs = self._handles(frames)
+            check(self._l.pvf_render_batch(self._h, ptr(hs), n, int(width), int(height), _yuv_flags(matrix, full_range), ptr(start), ptr(p),
+                                           ptr(text), len(text), C.c_void_p(int(out_ptr)) if out_ptr is not None else ptr(out),
+                                           1 if out_ptr is not None else 0))
+        return out
+
+    def render_rgb(self, frame, prims, width, height):
+        """the drawn picture before colour conversion, uint8 [height, width, 3] (pvf_debug_render_rgb)"""
+        from . import render as _render
+        _, p, text = _render.pack_primitives([prims])
+        out = np.empty((int(height), int(width), 3), np.uint8)
+        check(self._l.pvf_debug_render_rgb(self._h, self.stage(frame).handle, int(width), int(height), ptr(p), len(p), ptr(text), len(text),
+                                           ptr(out)))
+        return out
 
     def frame_from_yuv_device(self, y_ptr, y_pitch, u_ptr, v_ptr, c_pitch, height, width, layout="420", matrix="601", full_range=False,
                               c_step=1):

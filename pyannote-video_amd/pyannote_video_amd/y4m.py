@@ -100,6 +100,7 @@ def _parse_header(line, name):
             num, _, den = val.partition(":")
             if int(num) > 0 and int(den or 1) > 0:           # F0:0 = unknown
                 h["rate"] = int(num) / float(int(den or 1))
+                h["rate_tag"] = "%d:%d" % (int(num), int(den or 1))
         elif tag == "C":
             if val not in _C_TAGS:
                 raise IOError("%s: chroma format C%s is not supported (8-bit C420*, C422 and C444 are)" % (name, val))
@@ -153,6 +154,7 @@ class Y4mVideo(object):
         if rate is None:
             raise IOError("%s: the header names no frame rate; give one (--fps)" % self._name)
         self.frame_rate = float(rate)
+        self.rate_tag = hd.get("rate_tag")              # the header's own F tag, for a writer that passes the rate on (render.Y4mWriter)
         w, h = hd["width"], hd["height"]
         self._size = (w, h)
         self._frame_size = self._size
