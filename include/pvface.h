@@ -178,7 +178,7 @@ int32_t pvf_detector_screening(pvf_handle ctx, int32_t on, int32_t list_cap);
  * for every context the process creates. */
 int32_t pvf_detector_screening_stats(pvf_handle ctx, int64_t* batches, int64_t* listed, int64_t* retries, double* bounds, double* pipe_err);
 
-/* the embedder's convolutions on the f16 matrix cores with split operands (on by default; csrc/resnet.hip: conv_split_k).  on = 1:
+/* the embedder's convolutions on the f16 matrix cores with split operands (on by default; csrc/resnet.hip: conv_tile_k with ConvSplit).  on = 1:
  * every convolution outside the 32-channel stage runs as three f16 products of hi / lo halves (scaled by fixed powers of two) with an
  * fp32 accumulation -- descriptors within the error bound of DESIGN.md section 4, no longer the oracle's chain order; a face whose
  * activations leave the f16 range is embedded again on the exact kernels.  on = 0: the exact fp32 kernels only.  The environment

@@ -261,7 +261,7 @@ struct Ctx {
     int64_t screen_batches = 0, screen_listed = 0, screen_retries = 0;
     double screen_pipe_err = -1;              // measured by screen_probe: worst |pipe - exact| / sum of magnitudes over its K = 3200 accumulations (five cases)
     bool screen_pipe_flushes_subnormals = false;      // screen_probe case 4 (the bound carries the term e_sub either way)
-    // the embedder's convolutions on the f16 matrix cores with split operands (resnet.hip: conv_split_k; pvf_embedder_split)
+    // the embedder's convolutions on the f16 matrix cores with split operands (resnet.hip: conv_tile_k with ConvSplit; pvf_embedder_split)
     bool emb_split = true, emb_probe_done = false;
     DevBuf s_emb_flags, s_emb_redo;
     int64_t emb_split_faces = 0, emb_reruns = 0;

@@ -12,7 +12,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 // ---------------------------------------------------------------------------------------------------
@@ -61,21 +61,19 @@ struct ConvArgs {
     int ksz, stride, pad;
     int skip_mode;                     // 0 none, 1 identity [B][OH][OW][Cout], 2 avg-pool 2x2 s2 of x [B][XH][XW][XC]
     const float* skip; int XH, XW, XC, SH, SW;
-    // split path (conv_split_k): the weights as f16 hi / lo halves of (w * 2^w_exp), [Cout][Kpad / 32][32 hi, 32 lo]; activations are
+    // split form (ConvSplit): the weights as f16 hi / lo halves of (w * 2^w_exp), [Cout][Kpad / 32][32 hi, 32 lo]; activations are
     // scaled by 2^EMB_A_SCALE_EXP; out_scale = 2^-(w_exp + 8) undoes both; flags[face] = 1 when a scaled input would overflow f16
     const uint32_t* wsplit; float out_scale; int* flags;
 };
 
-// Implicit-GEMM convolution on v_mfma_f32_32x32x2_f32.  Block tile BM x BN = (64 WM) x (32 WN) output pixels x channels, 4 waves; a wave owns
-// a 64 x 32 tile = two 32 x 32 accumulators that share every B fragment.  K (= taps x input channels, the order of the oracle's chain)
-// advances in chunks of 32 through LDS; the next chunk's global loads are in flight during the MFMAs of the current one.
-// LDS layout: one row of 32 k-values per output pixel (A) / output channel (B), padded to 36 floats, with the even k first and the odd k
-// behind them (position (k >> 1) + 16 (k & 1)): lane (i, h) of a 32 x 32 x 2 MFMA needs k = 2 s + h for s = 0..15, i.e. 16 CONTIGUOUS floats
-// = 4 ds_read_b128 per 16 MFMAs (the 36-float pitch makes them conflict-free), instead of one ds_read_b32 per operand and MFMA.
-// Weights are stored transposed ([cout][K padded to 32], ctx.hip) so that both tiles are staged with the same 16-byte loads along k.
-// (Keeping the activations in that even / odd order in HBM as well -- so that a chunk could be staged with plain 16-byte copies -- was
-// measured 10 % SLOWER: the epilogue's stores and skip loads then scatter within each 128-byte line, and four scattered dwords per lane
-// quad cost the memory pipeline more than the 36 register moves per chunk that the split on the way into LDS costs.)
+// Implicit-GEMM convolution on the matrix cores: conv_tile_k, in two operand forms -- exact fp32 (ConvExact) and, the default, f16 hi / lo
+// split operands (ConvSplit; pvf_embedder_split).  A form names its weights, parks a 16-byte quad (k = 4 j4 .. 4 j4 + 3 of a row's chunk)
+// of A and of B in LDS, runs a chunk's MFMAs from a lane's row pointers and scales the sums; the kernel holds the rest.  Block tile
+// BM x BN = (64 WM) x (32 WN) output pixels x channels, 4 waves; a wave owns a 64 x 32 tile = two 32 x 32 accumulators that share every
+// B fragment.  K (= taps x input channels, the order of the oracle's chain) advances in chunks of 32 through LDS; the next chunk's global
+// loads are in flight during the MFMAs of the current one.  LDS: one row of 32 k-values per output pixel (A) / output channel (B), 32
+// dwords in either form, padded to 36; weights are stored transposed ([cout][K padded to 32], ctx.hip; the split form's: conv_wsplit_k),
+// a row Kpad / 4 sixteen-byte units in either form, so that both tiles are staged with the same 16-byte loads along k.
 
 // exact x / d for 0 <= x < 2^22, 1 <= d < 2^22 (rd = 1.0f / d): float estimate, one correction step.  Output pixel -> (face, row, column)
 // needs two divisions per tile row; 64-bit integer division is emulated with ~100 instructions, and 16 of them per thread took about as
@@ -89,7 +87,7 @@ __device__ __forceinline__ int small_div(int x, int d, float rd)
     return q;
 }
 
-// bias + affine + residual add + ReLU and the stores of one block's results (shared by the two K loops above / below); `smem` is free
+// bias + affine + residual add + ReLU and the stores of one block's results (shared by both operand forms of conv_tile_k); `smem` is free
 // after the K loop's last barrier and takes each wave's 64 x 32 tile for the transposing store path
 template <int WM, int WN>
 __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, float* smem, const f32x16& acc0, const f32x16& acc1, long M, long m0, int n0,
@@ -160,16 +158,95 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, float* smem, co
         }
 }
 
-template <int WM, int WN>
-__global__ void __launch_bounds__(256) conv_mfma_k(ConvArgs a)
+// Exact fp32 on v_mfma_f32_32x32x2_f32.  A row holds the even k first and the odd k behind them (position (k >> 1) + 16 (k & 1)): lane
+// (i, h) of a 32 x 32 x 2 MFMA needs k = 2 s + h for s = 0..15, i.e. 16 CONTIGUOUS floats = 4 ds_read_b128 per 16 MFMAs (the 36-float
+// pitch makes them conflict-free), instead of one ds_read_b32 per operand and MFMA.
+// (Keeping the activations in that even / odd order in HBM as well -- so that a chunk could be staged with plain 16-byte copies -- was
+// measured 10 % SLOWER: the epilogue's stores and skip loads then scatter within each 128-byte line, and four scattered dwords per lane
+// quad cost the memory pipeline more than the 36 register moves per chunk that the split on the way into LDS costs.)
+struct ConvExact {
+    static constexpr bool FLAGS = false;
+    static constexpr int LANE_K = 16;                   // dwords between the two half-waves' parts of a row
+    static __device__ __forceinline__ const u32x4* weights(const ConvArgs& a) { return reinterpret_cast<const u32x4*>(a.w); }
+    static __device__ __forceinline__ bool park_a(uint32_t* row, int j4, const u32x4& v)         // -> whether f16 can hold the quad
+    {
+        *reinterpret_cast<uint2*>(row + 2 * j4) = make_uint2(v.x, v.z);            // k = 4 j4, 4 j4 + 2   (even half)
+        *reinterpret_cast<uint2*>(row + 2 * j4 + 16) = make_uint2(v.y, v.w);       // k = 4 j4 + 1, + 3    (odd half)
+        return true;
+    }
+    static __device__ __forceinline__ void park_b(uint32_t* row, int j4, const u32x4& v) { park_a(row, j4, v); }
+    static __device__ __forceinline__ void chunk(const uint32_t* pa0, const uint32_t* pa1, const uint32_t* pb, f32x16& acc0, f32x16& acc1)
+    {
+        f32x4 fa0[4], fa1[4], fb[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            fa0[q] = *reinterpret_cast<const f32x4*>(pa0 + 4 * q);
+            fa1[q] = *reinterpret_cast<const f32x4*>(pa1 + 4 * q);
+            fb[q] = *reinterpret_cast<const f32x4*>(pb + 4 * q);
+        }
+#pragma unroll
+        for (int s = 0; s < 16; ++s) {
+            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa0[s >> 2][s & 3], fb[s >> 2][s & 3], acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa1[s >> 2][s & 3], fb[s >> 2][s & 3], acc1, 0, 0, 0);
+        }
+    }
+    static __device__ __forceinline__ void scale(const ConvArgs&, f32x16&, f32x16&) {}
+};
+
+// Split f16 on v_mfma_f32_32x32x16_f16.  Every scaled operand is a pair of f16 halves, v = hi + lo + e with hi = f16(v), lo = f16(v - hi)
+// (v - hi is exact in fp32), and a product is three MFMA terms, hi.hi + hi.lo + lo.hi, accumulated in fp32 (DESIGN.md section 4 for the
+// bound).  The scales are fixed powers of two: activations x 2^8 (EMB_A_SCALE_EXP, the same for every layer and face), weights x 2^w_exp
+// per layer with the largest |w| in [2^14, 2^15) (from the weights at model load); the sums are multiplied by 2^-(8 + w_exp), exactly,
+// before the fp32 arithmetic of conv_epilogue.  No scale depends on the data, so a face's descriptor never depends on its batch-mates.
+// A scaled input that f16 cannot hold (|x| >= 65504 / 256) marks its face in a.flags; resnet_forward embeds those faces again in the
+// exact form.  A row holds the chunk's 32 hi halves (16 dwords), then its 32 lo halves: lane (i, h) of k-step s (k = 16 s + 8 h + j)
+// reads hi at dword 8 s + 4 h and lo 16 dwords behind, one ds_read_b128 each (conflict-free with the 36-dword pitch).  A is split on
+// the way into LDS; a quad of B (split once per model, conv_wsplit_k: j4 < 4 hi halves, j4 >= 4 lo halves) is copied as is.
+#define EMB_A_SCALE_EXP 8
+#define EMB_F16_LIMIT 65504.0f
+struct ConvSplit {
+    static constexpr bool FLAGS = true;
+    static constexpr int LANE_K = 4;
+    static __device__ __forceinline__ const u32x4* weights(const ConvArgs& a) { return reinterpret_cast<const u32x4*>(a.wsplit); }
+    static __device__ __forceinline__ bool park_a(uint32_t* row, int j4, const u32x4& v)
+    {
+        const f32x4 xv = __builtin_bit_cast(f32x4, v) * (float)(1 << EMB_A_SCALE_EXP);   // (the whole vector: a bit_cast of one element read element 0)
+        // every value on its own: a NaN fails its comparison (fmaxf over the four would drop a NaN that stands next to a number, and
+        // the face would not be marked); a row without a pixel loads zeros only
+        const bool ok = __builtin_reduce_and(__builtin_elementwise_abs(xv) < EMB_F16_LIMIT);
+        const f16x4 hi = __builtin_convertvector(xv, f16x4), lo = __builtin_convertvector(xv - __builtin_convertvector(hi, f32x4), f16x4);
+        *reinterpret_cast<u32x2*>(row + 2 * j4) = __builtin_bit_cast(u32x2, hi);
+        *reinterpret_cast<u32x2*>(row + 2 * j4 + 16) = __builtin_bit_cast(u32x2, lo);
+        return ok;
+    }
+    static __device__ __forceinline__ void park_b(uint32_t* row, int j4, const u32x4& v) { *reinterpret_cast<u32x4*>(row + 4 * j4) = v; }
+    static __device__ __forceinline__ void chunk(const uint32_t* pa0, const uint32_t* pa1, const uint32_t* pb, f32x16& acc0, f32x16& acc1)
+    {
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const f16x8 ah0 = *reinterpret_cast<const f16x8*>(pa0 + 8 * s), al0 = *reinterpret_cast<const f16x8*>(pa0 + 16 + 8 * s);
+            const f16x8 ah1 = *reinterpret_cast<const f16x8*>(pa1 + 8 * s), al1 = *reinterpret_cast<const f16x8*>(pa1 + 16 + 8 * s);
+            const f16x8 bh = *reinterpret_cast<const f16x8*>(pb + 8 * s), bl = *reinterpret_cast<const f16x8*>(pb + 16 + 8 * s);
+            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah0, bh, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah1, bh, acc1, 0, 0, 0);
+            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah0, bl, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah1, bl, acc1, 0, 0, 0);
+            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al0, bh, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al1, bh, acc1, 0, 0, 0);
+        }
+    }
+    static __device__ __forceinline__ void scale(const ConvArgs& a, f32x16& acc0, f32x16& acc1) { acc0 *= a.out_scale; acc1 *= a.out_scale; }
+};
+
+template <int WM, int WN, class Ops>
+__global__ void __launch_bounds__(256) conv_tile_k(ConvArgs a)
 {
     constexpr int BM = 64 * WM, BN = 32 * WN, KC = 32, PITCH = 36;
     static_assert(WM * WN == 4, "four waves per block");
-    // A tile, B tile; after the K loop the same space takes each wave's 64 x 32 results for the transposing epilogue
-    constexpr int SM_ROWS = (BM + BN > 256) ? BM + BN : 256;
+    constexpr int SM_ROWS = (BM + BN > 256) ? BM + BN : 256;         // A tile, B tile; after the K loop each wave's 64 x 32 results
     __shared__ __attribute__((aligned(16))) float smem[SM_ROWS * PITCH];
-    float* As = smem;
-    float* Bs = smem + BM * PITCH;
+    uint32_t* As = reinterpret_cast<uint32_t*>(smem);
+    uint32_t* Bs = As + BM * PITCH;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WN, wn = wave % WN;
     const long M = (long)a.B * a.OH * a.OW;
@@ -179,13 +256,12 @@ __global__ void __launch_bounds__(256) conv_mfma_k(ConvArgs a)
 #pragma unroll
     for (int i = 0; i < 16; ++i) { acc0[i] = 0.0f; acc1[i] = 0.0f; }
 
-    // staging roles: A tile = BM rows x 8 float4 (4 consecutive k = 4 input channels of one tap), B tile = BN rows x 8 float4.
+    // staging roles: A tile = BM rows x 8 quads (4 consecutive k = 4 input channels of one tap), B tile = BN rows x 8 quads.
     // Input pixels are fetched with raw buffer loads: a tap that falls outside the image (or a row past M, or k past K) gets an offset
     // beyond the buffer and comes back as zeros -- no branch around any load, so the address arithmetic of the next chunk is one
     // straight-line block the scheduler spreads between the MFMAs of the current one.
     constexpr int A_F4 = BM * 8 / 256, B_F4 = BN * 8 / 256;
-    constexpr int RSRC_FLAGS = 0x00020000;
-    constexpr int OOB = (int)0x80000000;
+    constexpr int RSRC_FLAGS = 0x00020000, OOB = (int)0x80000000;
     const int hw = a.OH * a.OW;
     const int b_first = (int)(m0 / hw);                                    // the tile's first face: offsets below stay small (scalar)
     const int rel0 = (int)(m0 - (long)b_first * hw);                       // tile rows are rel0 + i within [first face ...): < hw + BM
@@ -213,12 +289,11 @@ __global__ void __launch_bounds__(256) conv_mfma_k(ConvArgs a)
         }
     }
     const int Kpad = (a.K + KC - 1) / KC * KC;
-    const int j4 = tid & 7;                             // which float4 of a row this thread moves
-    const float* wrow[B_F4];
+    const int j4 = tid & 7;                             // which quad of a row this thread moves
+    const u32x4* wrow[B_F4];
 #pragma unroll
-    for (int q = 0; q < B_F4; ++q) wrow[q] = a.w + (size_t)(n0 + ((tid + q * 256) >> 3)) * Kpad + 4 * j4;
-    u32x4 va[A_F4];
-    float4 vb[B_F4];
+    for (int q = 0; q < B_F4; ++q) wrow[q] = Ops::weights(a) + (size_t)(n0 + ((tid + q * 256) >> 3)) * (Kpad / 4) + j4;
+    u32x4 va[A_F4], vb[B_F4];
     // Three stages per chunk, one chunk apart: its byte offsets are worked out (plain VALU work, spread between the MFMAs of an earlier
     // chunk), its loads are issued right after the barrier of the chunk before it, and it is parked in LDS one barrier later.
     // Chunk walk: (tap row, tap column, first channel) advance with scalar adds, no division in the loop (input channels: a multiple of 32).
@@ -236,7 +311,7 @@ __global__ void __launch_bounds__(256) conv_mfma_k(ConvArgs a)
             const int ok = k_ok & -(int)((unsigned)iy < (unsigned)a.H) & -(int)((unsigned)ix < (unsigned)a.W);
             voff[q] = (((pa_off[q] + delta) * 4) & ok) | (OOB & ~ok);
         }
-        woff = f_k;
+        woff = f_k >> 2;                                // sixteen-byte units: a chunk's row is 8 of them
         if (f_k + KC < Kpad) {                          // (past the last chunk: stay on it; those loads are issued but never parked)
             f_k += KC;
             f_c += KC;
@@ -247,26 +322,23 @@ __global__ void __launch_bounds__(256) conv_mfma_k(ConvArgs a)
 #pragma unroll
         for (int q = 0; q < A_F4; ++q) va[q] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, voff[q], 0, 0);
 #pragma unroll
-        for (int q = 0; q < B_F4; ++q) vb[q] = *reinterpret_cast<const float4*>(wrow[q] + woff);     // zero-padded beyond K
+        for (int q = 0; q < B_F4; ++q) vb[q] = wrow[q][woff];                                        // zero-padded beyond K
     };
     auto park = [&]() {
+        int bad = 0;                                    // bit q: slot q holds a value that f16 cannot take
 #pragma unroll
-        for (int q = 0; q < A_F4; ++q) {
-            uint32_t* row = reinterpret_cast<uint32_t*>(&As[((tid + q * 256) >> 3) * PITCH + 2 * j4]);
-            *reinterpret_cast<uint2*>(row) = make_uint2(va[q].x, va[q].z);          // k = 4 j4, 4 j4 + 2   (even half)
-            *reinterpret_cast<uint2*>(row + 16) = make_uint2(va[q].y, va[q].w);     // k = 4 j4 + 1, + 3    (odd half)
-        }
+        for (int q = 0; q < A_F4; ++q) bad |= Ops::park_a(&As[((tid + q * 256) >> 3) * PITCH], j4, va[q]) ? 0 : (1 << q);
 #pragma unroll
-        for (int q = 0; q < B_F4; ++q) {
-            float* row = &Bs[((tid + q * 256) >> 3) * PITCH + 2 * j4];
-            *reinterpret_cast<float2*>(row) = make_float2(vb[q].x, vb[q].z);
-            *reinterpret_cast<float2*>(row + 16) = make_float2(vb[q].y, vb[q].w);
-        }
+        for (int q = 0; q < B_F4; ++q) Ops::park_b(&Bs[((tid + q * 256) >> 3) * PITCH], j4, vb[q]);
+        if constexpr (Ops::FLAGS)
+            if (bad)
+                for (int q = 0; q < A_F4; ++q)
+                    if ((bad >> q) & 1) a.flags[b_first + small_div(rel0 + ((tid + q * 256) >> 3), hw, r_hw)] = 1;
     };
     const int li = lane & 31, kh = lane >> 5;
-    const float* pa0 = &As[(wm * 64 + li) * PITCH + 16 * kh];
-    const float* pa1 = pa0 + 32 * PITCH;
-    const float* pb = &Bs[(wn * 32 + li) * PITCH + 16 * kh];
+    const uint32_t* pa0 = &As[(wm * 64 + li) * PITCH + Ops::LANE_K * kh];
+    const uint32_t* pa1 = pa0 + 32 * PITCH;
+    const uint32_t* pb = &Bs[(wn * 32 + li) * PITCH + Ops::LANE_K * kh];
     offsets();
     issue();
     offsets();
@@ -276,20 +348,10 @@ __global__ void __launch_bounds__(256) conv_mfma_k(ConvArgs a)
         issue();                                      // chunk k0 + KC: in flight during all of this chunk's MFMAs
         __builtin_amdgcn_sched_barrier(0);
         offsets();                                    // chunk k0 + 2 KC
-        f32x4 fa0[4], fa1[4], fb[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            fa0[q] = *reinterpret_cast<const f32x4*>(pa0 + 4 * q);
-            fa1[q] = *reinterpret_cast<const f32x4*>(pa1 + 4 * q);
-            fb[q] = *reinterpret_cast<const f32x4*>(pb + 4 * q);
-        }
-#pragma unroll
-        for (int s = 0; s < 16; ++s) {
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa0[s >> 2][s & 3], fb[s >> 2][s & 3], acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa1[s >> 2][s & 3], fb[s >> 2][s & 3], acc1, 0, 0, 0);
-        }
+        Ops::chunk(pa0, pa1, pb, acc0, acc1);
         __syncthreads();
     }
+    Ops::scale(a, acc0, acc1);
     conv_epilogue<WM, WN>(a, smem, acc0, acc1, M, m0, n0, rel0, b_first, hw, r_hw, r_ow, wave, lane);
 }
 
@@ -297,20 +359,6 @@ __global__ void __launch_bounds__(256) conv_mfma_k(ConvArgs a)
 // profiles/r04_conv_lds_vs_regs.txt -- and a spatial input tile reused across the 9 taps, one fetch per pixel and one barrier per block,
 // round 5 -- profiles/r05_conv_band_experiment.txt: a layer's MFMAs and its unavoidable HBM traffic are of the same size and run one
 // after the other inside a block; the staging of the A operand is not what the matrix pipe waits for.)
-
-// ---------------------------------------------------------------------------------------------------
-// The same convolution on the f16 matrix cores with split operands (the default; pvf_embedder_split).  Every scaled operand is a pair
-// of f16 halves, v = hi + lo + e with hi = f16(v), lo = f16(v - hi) (v - hi is exact in fp32), and a product is three
-// v_mfma_f32_32x32x16_f16 terms, hi.hi + hi.lo + lo.hi, accumulated in fp32 (DESIGN.md section 4 for the bound).  The scales are fixed
-// powers of two: activations x 2^8 (EMB_A_SCALE_EXP, the same for every layer and face), weights x 2^w_exp per layer with the
-// largest |w| in [2^14, 2^15) (from the weights at model load); the epilogue multiplies by 2^-(8 + w_exp), exactly, before the fp32
-// arithmetic of conv_epilogue.  No scale depends on the data, so a face's descriptor never depends on its batch-mates.  A scaled input
-// that f16 cannot hold (|x| >= 65504 / 256) marks its face in a.flags; resnet_forward embeds those faces again on the exact kernels.
-// Tiles and staging are conv_mfma_k's; an LDS row holds a chunk's 32 hi halves (16 dwords), then its 32 lo halves, padded to 36
-// dwords: lane (i, h) of k-step s (k = 16 s + 8 h + j) reads hi at dword 8 s + 4 h and lo 16 dwords behind, one ds_read_b128 each
-// (conflict-free with the 36-dword pitch).  A is split on the way into LDS; B (split once per model, conv_wsplit_k) is copied as is.
-#define EMB_A_SCALE_EXP 8
-#define EMB_F16_LIMIT 65504.0f
 
 // w [cout][Kpad] fp32 -> out [cout][Kpad / 32][32 hi, 32 lo] f16 of w * 2^w_exp
 __global__ void __launch_bounds__(256) conv_wsplit_k(const float* __restrict__ w, int total, int w_exp, _Float16* __restrict__ out)
@@ -325,145 +373,8 @@ __global__ void __launch_bounds__(256) conv_wsplit_k(const float* __restrict__ w
     out[(size_t)row32 * 64 + 32 + kk] = lo;
 }
 
-template <int WM, int WN>
-__global__ void __launch_bounds__(256) conv_split_k(ConvArgs a)
-{
-    constexpr int BM = 64 * WM, BN = 32 * WN, KC = 32, PITCH = 36;
-    static_assert(WM * WN == 4, "four waves per block");
-    constexpr int SM_ROWS = (BM + BN > 256) ? BM + BN : 256;
-    __shared__ __attribute__((aligned(16))) float smem[SM_ROWS * PITCH];
-    uint32_t* As = reinterpret_cast<uint32_t*>(smem);
-    uint32_t* Bs = As + BM * PITCH;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave / WN, wn = wave % WN;
-    const long M = (long)a.B * a.OH * a.OW;
-    const long m0 = (long)blockIdx.x * BM;
-    const int n0 = blockIdx.y * BN;
-    f32x16 acc0, acc1;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { acc0[i] = 0.0f; acc1[i] = 0.0f; }
-
-    constexpr int A_F4 = BM * 8 / 256, B_F4 = BN * 8 / 256;
-    constexpr int RSRC_FLAGS = 0x00020000;
-    constexpr int OOB = (int)0x80000000;
-    const int hw = a.OH * a.OW;
-    const int b_first = (int)(m0 / hw);
-    const int rel0 = (int)(m0 - (long)b_first * hw);
-    const float r_hw = 1.0f / (float)hw, r_ow = 1.0f / (float)a.OW;
-    const size_t face = (size_t)a.H * a.W * a.Cin;
-    const size_t in_bytes = (size_t)(a.B - b_first) * face * sizeof(float);
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc((void*)(a.in + (size_t)b_first * face), 0,
-                                                                           in_bytes > 0x7ffffff0u ? 0x7ffffff0 : (int)in_bytes, RSRC_FLAGS);
-    int pa_off[A_F4], pa_y[A_F4], pa_x[A_F4];
-#pragma unroll
-    for (int q = 0; q < A_F4; ++q) {
-        const int i = (tid + q * 256) >> 3;
-        const long m = m0 + i;
-        pa_off[q] = 0; pa_y[q] = -(1 << 20); pa_x[q] = 0;
-        if (m < M) {
-            const int rel = rel0 + i;
-            const int bb = small_div(rel, hw, r_hw);
-            const int rem = rel - bb * hw;
-            const int oy = small_div(rem, a.OW, r_ow);
-            const int ox = rem - oy * a.OW;
-            if (oy < a.AH && ox < a.AW) {
-                pa_y[q] = oy * a.stride - a.pad; pa_x[q] = ox * a.stride - a.pad;
-                pa_off[q] = ((bb * a.H + pa_y[q]) * a.W + pa_x[q]) * a.Cin;
-            }
-        }
-    }
-    const int Kpad = (a.K + KC - 1) / KC * KC;
-    const int j4 = tid & 7;
-    const u32x4* wrow[B_F4];                            // 16 bytes of a row's chunk: j4 < 4 hi halves, j4 >= 4 lo halves
-#pragma unroll
-    for (int q = 0; q < B_F4; ++q) wrow[q] = reinterpret_cast<const u32x4*>(a.wsplit) + (size_t)(n0 + ((tid + q * 256) >> 3)) * (Kpad / 4) + j4;
-    u32x4 va[A_F4], vb[B_F4];
-    int f_r = 0, f_s = 0, f_c = 0, f_k = 0;
-    int voff[A_F4], woff = 0;
-    auto offsets = [&]() {
-        const int kq = f_k + 4 * j4;
-        const int r = f_r, sft = f_s;
-        const int delta = (r * a.W + sft) * a.Cin + f_c + 4 * j4;
-        const int k_ok = (kq < a.K) ? -1 : 0;
-#pragma unroll
-        for (int q = 0; q < A_F4; ++q) {
-            const int iy = pa_y[q] + r, ix = pa_x[q] + sft;
-            const int ok = k_ok & -(int)((unsigned)iy < (unsigned)a.H) & -(int)((unsigned)ix < (unsigned)a.W);
-            voff[q] = (((pa_off[q] + delta) * 4) & ok) | (OOB & ~ok);
-        }
-        woff = f_k / 4;                                 // uint4 units: a chunk's row is 8 of them
-        if (f_k + KC < Kpad) {
-            f_k += KC;
-            f_c += KC;
-            if (f_c >= a.Cin) { f_c = 0; if (++f_s == a.ksz) { f_s = 0; ++f_r; } }
-        }
-    };
-    auto issue = [&]() {
-#pragma unroll
-        for (int q = 0; q < A_F4; ++q) va[q] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, voff[q], 0, 0);
-#pragma unroll
-        for (int q = 0; q < B_F4; ++q) vb[q] = wrow[q][woff];
-    };
-    const float sa = (float)(1 << EMB_A_SCALE_EXP);
-    auto park = [&]() {
-        int bad = 0;                                    // bit q: slot q holds a value that f16 cannot take
-#pragma unroll
-        for (int q = 0; q < A_F4; ++q) {
-            const f32x4 xv = __builtin_bit_cast(f32x4, va[q]) * sa;       // (the whole vector: a bit_cast of one element read element 0)
-            const float x0 = xv.x, x1 = xv.y, x2 = xv.z, x3 = xv.w;
-            // every value on its own: a NaN fails its comparison (fmaxf over the four would drop a NaN that stands next to a number, and
-            // the face would not be marked); a row without a pixel loads zeros only
-            const int ok = (int)(fabsf(x0) < EMB_F16_LIMIT) & (int)(fabsf(x1) < EMB_F16_LIMIT) & (int)(fabsf(x2) < EMB_F16_LIMIT) &
-                           (int)(fabsf(x3) < EMB_F16_LIMIT);
-            bad |= ok ? 0 : (1 << q);
-            const _Float16 h0 = (_Float16)x0, h1 = (_Float16)x1, h2 = (_Float16)x2, h3 = (_Float16)x3;
-            const f16x2 h01 = {h0, h1}, h23 = {h2, h3};
-            const f16x2 l01 = {(_Float16)(x0 - (float)h0), (_Float16)(x1 - (float)h1)};
-            const f16x2 l23 = {(_Float16)(x2 - (float)h2), (_Float16)(x3 - (float)h3)};
-            uint32_t* row = &As[((tid + q * 256) >> 3) * PITCH + 2 * j4];
-            *reinterpret_cast<u32x2*>(row) = (u32x2){__builtin_bit_cast(uint32_t, h01), __builtin_bit_cast(uint32_t, h23)};
-            *reinterpret_cast<u32x2*>(row + 16) = (u32x2){__builtin_bit_cast(uint32_t, l01), __builtin_bit_cast(uint32_t, l23)};
-        }
-#pragma unroll
-        for (int q = 0; q < B_F4; ++q) *reinterpret_cast<u32x4*>(&Bs[((tid + q * 256) >> 3) * PITCH + 4 * j4]) = vb[q];
-        if (bad)
-            for (int q = 0; q < A_F4; ++q)
-                if ((bad >> q) & 1) a.flags[b_first + small_div(rel0 + ((tid + q * 256) >> 3), hw, r_hw)] = 1;
-    };
-    const int li = lane & 31, kh = lane >> 5;
-    const uint32_t* pa0 = &As[(wm * 64 + li) * PITCH + 4 * kh];
-    const uint32_t* pa1 = pa0 + 32 * PITCH;
-    const uint32_t* pb = &Bs[(wn * 32 + li) * PITCH + 4 * kh];
-    offsets();
-    issue();
-    offsets();
-    for (int k0 = 0; k0 < Kpad; k0 += KC) {
-        park();
-        __syncthreads();
-        issue();
-        __builtin_amdgcn_sched_barrier(0);
-        offsets();
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            const f16x8 ah0 = *reinterpret_cast<const f16x8*>(pa0 + 8 * s), al0 = *reinterpret_cast<const f16x8*>(pa0 + 16 + 8 * s);
-            const f16x8 ah1 = *reinterpret_cast<const f16x8*>(pa1 + 8 * s), al1 = *reinterpret_cast<const f16x8*>(pa1 + 16 + 8 * s);
-            const f16x8 bh = *reinterpret_cast<const f16x8*>(pb + 8 * s), bl = *reinterpret_cast<const f16x8*>(pb + 16 + 8 * s);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah0, bh, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah1, bh, acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah0, bl, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah1, bl, acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al0, bh, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al1, bh, acc1, 0, 0, 0);
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { acc0[i] *= a.out_scale; acc1[i] *= a.out_scale; }
-    conv_epilogue<WM, WN>(a, smem, acc0, acc1, M, m0, n0, rel0, b_first, hw, r_hw, r_ow, wave, lane);
-}
-
-// What conv_split_k takes for granted about the device, checked once per context (a mismatch is an error, not a fallback): lanes
-// (row, k octet) of A and (column, k octet) of B meet in v_mfma_f32_32x32x16_f16 as the kernel's LDS reads assume, lane (column, row
+// What the split form takes for granted about the device, checked once per context (a mismatch is an error, not a fallback): lanes
+// (row, k octet) of A and (column, k octet) of B meet in v_mfma_f32_32x32x16_f16 as ConvSplit's LDS reads assume, lane (column, row
 // group) receives D as conv_epilogue assumes, and an accumulation of K products inside the matrix pipe stays within the allowance of
 // the error bound (2^-22 per addition relative to the sum of the terms' magnitudes: DESIGN.md section 4).  One wave; a, b in lane order.
 __global__ void __launch_bounds__(64) embed_probe_k(const uint4* __restrict__ a, const uint4* __restrict__ b, int steps, float* __restrict__ d)
@@ -757,13 +668,21 @@ __global__ void __launch_bounds__(256) head_k(const float* __restrict__ x, int H
     }
 }
 
+// the layers that conv3x3_c32_k takes: 3 x 3, stride 1, pad 1, 32 -> 32 channels on the 35 x 35 map, all of it convolved, no averaged skip
+static bool conv_is_c32(const ConvArgs& a)
+{
+    return a.Cin == 32 && a.Cout == 32 && a.H == 35 && a.W == 35 && a.OH == 35 && a.OW == 35 && a.AH == 35 && a.AW == 35 && a.ksz == 3 &&
+           a.stride == 1 && a.pad == 1 && a.skip_mode != 2;
+}
+
 static void launch_conv(Ctx* c, const ConvArgs& a)
 {
     const long M = (long)a.B * a.OH * a.OW;
     PVF_REQUIRE(a.Cin % 32 == 0, "conv: input channels must be a multiple of 32 (the 3-channel first layer has a kernel of its own: stem_conv_k)");
     PVF_REQUIRE(a.OH * a.OW < (1 << 21) && a.Cout % 32 == 0, "conv: output map too large for the kernel's index arithmetic / Cout not a multiple of 32");
-    if (a.frag && a.Cin == 32 && a.Cout == 32 && a.H == 35 && a.W == 35 && a.OH == 35 && a.OW == 35 && a.AH == 35 && a.AW == 35 && a.ksz == 3 &&
-        a.stride == 1 && a.pad == 1 && a.skip_mode != 2) {
+    // (a tile shape's kernel in the operand form a's weights come in)
+    auto tile = [&](auto exact, auto split, dim3 grid) { hipLaunchKernelGGL((a.wsplit ? split : exact), grid, dim3(256), 0, c->stream, a); };
+    if (a.frag && conv_is_c32(a)) {
         static std::atomic<uint64_t> attr_set{0};             // per device (a function attribute belongs to the device it was set on)
         const size_t lds = (size_t)(C32_TILE_FLOATS + 144 * 64) * sizeof(float);
         const uint64_t bit = 1ull << (c->device & 63);
@@ -775,14 +694,10 @@ static void launch_conv(Ctx* c, const ConvArgs& a)
         hipLaunchKernelGGL(conv3x3_c32_k, dim3((unsigned)std::min(items, 2 * c->n_cu)), dim3(256), lds, c->stream, a.in, a.frag, a.bias, a.gamma, a.beta,
                            a.skip_mode == 1 ? a.skip : nullptr, a.out, items);
     } else if (a.Cout == 32) {
-        const dim3 grid((unsigned)((M + 255) / 256), 1);
-        if (a.wsplit) hipLaunchKernelGGL((conv_split_k<4, 1>), grid, dim3(256), 0, c->stream, a);
-        else hipLaunchKernelGGL((conv_mfma_k<4, 1>), grid, dim3(256), 0, c->stream, a);
+        tile(conv_tile_k<4, 1, ConvExact>, conv_tile_k<4, 1, ConvSplit>, dim3((unsigned)((M + 255) / 256), 1));
     } else {
         PVF_REQUIRE(a.Cout % 64 == 0, "conv: Cout must be 32 or a multiple of 64");
-        const dim3 grid((unsigned)((M + 127) / 128), a.Cout / 64);
-        if (a.wsplit) hipLaunchKernelGGL((conv_split_k<2, 2>), grid, dim3(256), 0, c->stream, a);
-        else hipLaunchKernelGGL((conv_mfma_k<2, 2>), grid, dim3(256), 0, c->stream, a);
+        tile(conv_tile_k<2, 2, ConvExact>, conv_tile_k<2, 2, ConvSplit>, dim3((unsigned)((M + 127) / 128), a.Cout / 64));
     }
 }
 
@@ -828,14 +743,14 @@ void conv_layer_free(ConvLayer& L)
     L.d_wsplit = nullptr;
 }
 
-// the weight side of a's launch: d_w, and what the layer's kernel wants beside it, made on first use -- the fragment order for a
-// 32 -> 32 3 x 3 layer (conv3x3_c32_k; `generic`: not even there), else with `split` the f16 halves and their scale
+// the weight side of a's launch (its geometry is filled in): d_w, and what the layer's kernel wants beside it, made on first use -- the
+// fragment order for conv3x3_c32_k's layers (`generic`: not even there), else with `split` the f16 halves and their scale
 static void conv_bind_weights(Ctx* c, ConvLayer& L, bool split, bool generic, int* flags, ConvArgs& a)
 {
     a.w = L.d_w; a.K = L.k * L.k * L.cin; a.bias = L.d_bias; a.gamma = L.d_gamma; a.beta = L.d_beta;
     a.frag = nullptr; a.wsplit = nullptr; a.out_scale = 0.0f; a.flags = nullptr;
-    const bool own = !generic && L.cin == 32 && L.cout == 32 && L.k == 3;
-    if (own) {
+    if (!generic && L.cin == 32 && L.cout == 32 && L.k == 3) {     // a 32 -> 32 3 x 3 layer is never split: exact fp32 on any map
+        if (!conv_is_c32(a)) return;                                // (a map other than conv3x3_c32_k's: only pvf_debug_conv brings one)
         if (!L.d_frag) {
             HIP_CHECK(hipMalloc(&L.d_frag, 144 * 64 * sizeof(float)));
             hipLaunchKernelGGL(conv_frag_k, dim3(144), dim3(64), 0, c->stream, L.d_w, 288, L.d_frag);
@@ -856,7 +771,7 @@ static void conv_bind_weights(Ctx* c, ConvLayer& L, bool split, bool generic, in
     a.flags = flags;
 }
 
-// ---- embed_probe: the f16 matrix pipe against what conv_split_k assumes (once per context, before the first split forward) ----------
+// ---- embed_probe: the f16 matrix pipe against what the split form assumes (once per context, before the first split forward) ----------
 static uint16_t f16_bits(float v)
 {
     const _Float16 h = (_Float16)v;                     // host conversion: round to nearest even
@@ -929,10 +844,20 @@ static void embed_probe(Ctx* c)
     (void)hipFree(dev);
     c->emb_pipe_err = worst;
     PVF_REQUIRE(worst <= (double)K * std::ldexp(1.0, -22),
-                "embed_probe: v_mfma_f32_32x32x16_f16 does not place or accumulate as the split embedder (conv_split_k) assumes on this device");
+                "embed_probe: v_mfma_f32_32x32x16_f16 does not place or accumulate as the split embedder (conv_tile_k's ConvSplit) assumes on this device");
 }
 
-// d_chips: [n][150][150][3] u8 on device; h_out [n][128]; split: the convolutions outside the 32-channel stage on conv_split_k, and
+// The 14 residual units: input channels, output channels, down-sampling (a stride-2 `a` layer without padding and the 2 x 2 averaged skip)
+static const int UN[14][3] = {{32, 32, 0}, {32, 32, 0}, {32, 32, 0}, {32, 64, 1}, {64, 64, 0}, {64, 64, 0}, {64, 64, 0},
+                              {64, 128, 1}, {128, 128, 0}, {128, 128, 0}, {128, 256, 1}, {256, 256, 0}, {256, 256, 0}, {256, 256, 1}};
+struct UnitDims { int a, s, o; };                        // sides of the `a` layer's output, of the skip map and of the unit's output
+static UnitDims unit_dims(int u, int H)                  // unit u on an input map of side H (the maps are square)
+{
+    const int a = UN[u][2] ? 1 + (H - 3) / 2 : H, s = UN[u][2] ? 1 + (H - 2) / 2 : H;
+    return {a, s, std::max(a, s)};
+}
+
+// d_chips: [n][150][150][3] u8 on device; h_out [n][128]; split: the convolutions outside the 32-channel stage in the split form, and
 // h_flags[n] = 1 for the faces whose activations left its range
 // tap (stage access, or null): the activation after tap->stage is copied to tap->h_out as well; launches, buffers and results are the same
 static void resnet_run(Ctx* c, const uint8_t* d_chips, int n, float* h_out, bool split, int* h_flags, const EmbedTap* tap = nullptr)
@@ -976,9 +901,7 @@ static void resnet_run(Ctx* c, const uint8_t* d_chips, int n, float* h_out, bool
         tapped(1, z, B, hp, hp, 32);
         // rotate buffers: cur = z (unit input), t1/t2 scratch
         float* cur = z; float* t1 = x; float* t2 = y;
-        int H = hp, W = hp;
-        static const int UN[14][3] = {{32, 32, 0}, {32, 32, 0}, {32, 32, 0}, {32, 64, 1}, {64, 64, 0}, {64, 64, 0}, {64, 64, 0},
-                                      {64, 128, 1}, {128, 128, 0}, {128, 128, 0}, {128, 256, 1}, {256, 256, 0}, {256, 256, 0}, {256, 256, 1}};
+        int H = hp;
         int* flags = nullptr;
         if (split) {
             flags = c->s_emb_flags.as<int>();
@@ -989,29 +912,26 @@ static void resnet_run(Ctx* c, const uint8_t* d_chips, int n, float* h_out, bool
             ConvLayer& La = c->emb.convs[1 + 2 * u];
             ConvLayer& Lb = c->emb.convs[2 + 2 * u];
             const int stride = down ? 2 : 1, pad = down ? 0 : 1;
-            const int ah = 1 + (H + 2 * pad - 3) / stride, aw = 1 + (W + 2 * pad - 3) / stride;
+            const auto [ah, sh, oh] = unit_dims(u, H);
             memset(&a, 0, sizeof a);
-            a.in = cur; a.B = B; a.H = H; a.W = W; a.Cin = cin;
-            a.out = t1; a.OH = ah; a.OW = aw; a.Cout = nn; a.AH = ah; a.AW = aw; a.ksz = 3; a.stride = stride; a.pad = pad; a.skip_mode = 0;
+            a.in = cur; a.B = B; a.H = H; a.W = H; a.Cin = cin;
+            a.out = t1; a.OH = ah; a.OW = ah; a.Cout = nn; a.AH = ah; a.AW = ah; a.ksz = 3; a.stride = stride; a.pad = pad; a.skip_mode = 0;
             conv_bind_weights(c, La, split, false, flags, a);
             launch_conv(c, a);
-            tapped(2 + 2 * u, t1, B, ah, aw, nn);
-            int sh = H, sw = W;
-            if (down) { sh = 1 + (H - 2) / 2; sw = 1 + (W - 2) / 2; }
-            const int oh = std::max(ah, sh), ow = std::max(aw, sw);
+            tapped(2 + 2 * u, t1, B, ah, ah, nn);
             memset(&a, 0, sizeof a);
-            a.in = t1; a.B = B; a.H = ah; a.W = aw; a.Cin = nn;
-            a.out = t2; a.OH = oh; a.OW = ow; a.Cout = nn; a.AH = ah; a.AW = aw; a.ksz = 3; a.stride = 1; a.pad = 1;
-            a.skip_mode = down ? 2 : 1; a.skip = cur; a.XH = H; a.XW = W; a.XC = cin; a.SH = sh; a.SW = sw;
+            a.in = t1; a.B = B; a.H = ah; a.W = ah; a.Cin = nn;
+            a.out = t2; a.OH = oh; a.OW = oh; a.Cout = nn; a.AH = ah; a.AW = ah; a.ksz = 3; a.stride = 1; a.pad = 1;
+            a.skip_mode = down ? 2 : 1; a.skip = cur; a.XH = H; a.XW = H; a.XC = cin; a.SH = sh; a.SW = sh;
             conv_bind_weights(c, Lb, split, false, flags, a);
             launch_conv(c, a);
-            tapped(3 + 2 * u, t2, B, oh, ow, nn);
+            tapped(3 + 2 * u, t2, B, oh, oh, nn);
             float* old = cur; cur = t2; t2 = old;
-            H = oh; W = ow;
+            H = oh;
         }
         float* d_out = reinterpret_cast<float*>(c->s_act2.as<uint8_t>() + (size_t)cap * hp * hp * 32 * sizeof(float));
         // cur may alias s_act2's front part; the embedding slot sits behind it
-        hipLaunchKernelGGL(head_k, dim3(B), dim3(256), 0, c->stream, cur, H * W, e.d_fc, d_out);
+        hipLaunchKernelGGL(head_k, dim3(B), dim3(256), 0, c->stream, cur, H * H, e.d_fc, d_out);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipMemcpyAsync(h_out + (size_t)b0 * 128, d_out, (size_t)B * 128 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
         if (split) HIP_CHECK(hipMemcpyAsync(h_flags + b0, flags, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -1054,10 +974,9 @@ void resnet_debug_stage(Ctx* c, const uint8_t* d_chips, int n, bool split, Embed
         int H = 72, C = 32;
         if (tap->stage >= 1) H = 35;
         for (int u = 0; 2 + 2 * u <= tap->stage; ++u) {
-            static const int UN[14][2] = {{32, 0}, {32, 0}, {32, 0}, {64, 1}, {64, 0}, {64, 0}, {64, 0}, {128, 1}, {128, 0}, {128, 0}, {256, 1}, {256, 0}, {256, 0}, {256, 1}};
-            C = UN[u][0];
-            const int a = UN[u][1] ? 1 + (H - 3) / 2 : H, s = UN[u][1] ? 1 + (H - 2) / 2 : H;
-            H = (tap->stage == 2 + 2 * u) ? a : std::max(a, s);
+            C = UN[u][1];
+            const UnitDims d = unit_dims(u, H);
+            H = (tap->stage == 2 + 2 * u) ? d.a : d.o;
         }
         tap->dims[0] = H; tap->dims[1] = H; tap->dims[2] = C;
     }
@@ -1081,6 +1000,7 @@ struct ScopedLayer {
     ConvLayer L{};
     ~ScopedLayer() { conv_layer_free(L); }
 };
+struct Drain { Ctx* c; ~Drain() { (void)hipStreamSynchronize(c->stream); } };     // nothing of a debug call is in flight when its memory goes
 }
 
 void resnet_debug_conv(Ctx* c, const int32_t* g, const float* in, const float* w, const float* bias, const float* gamma, const float* beta,
@@ -1120,7 +1040,7 @@ void resnet_debug_conv(Ctx* c, const int32_t* g, const float* in, const float* w
     }
     a.in = reinterpret_cast<const float*>(d_in.p); a.out = reinterpret_cast<float*>(d_out.p);
     a.skip = n_skip ? reinterpret_cast<const float*>(d_skip.p) : nullptr;
-    struct Drain { Ctx* c; ~Drain() { (void)hipStreamSynchronize(c->stream); } } drain{c};     // nothing of this call is in flight when its memory goes
+    Drain drain{c};
     conv_bind_weights(c, sl.L, split, force_generic, d_flags, a);
     launch_conv(c, a);
     HIP_CHECK(hipGetLastError());
@@ -1138,7 +1058,7 @@ void resnet_debug_head(Ctx* c, const float* x, int n, int hw, float* out)
     PVF_REQUIRE(x && out && n > 0 && hw > 0 && (size_t)n * hw < (1u << 22), "pvf_debug_embed_head: bad arguments");
     const size_t n_x = (size_t)n * hw * 256;
     Scoped d_x(n_x * sizeof(float)), d_o((size_t)n * 128 * sizeof(float));
-    struct Drain { Ctx* c; ~Drain() { (void)hipStreamSynchronize(c->stream); } } drain{c};
+    Drain drain{c};
     HIP_CHECK(hipMemcpyAsync(d_x.p, x, n_x * sizeof(float), hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(head_k, dim3(n), dim3(256), 0, c->stream, reinterpret_cast<const float*>(d_x.p), hw, c->emb.d_fc, reinterpret_cast<float*>(d_o.p));
     HIP_CHECK(hipGetLastError());

@@ -987,7 +987,7 @@ class Context(object):
         return {"batches": b.value, "listed": n.value, "retries": r.value, "bounds": bounds[:5].tolist(), "pipe_err": pe.value}
 
     def embedder_split(self, on=True):
-        """the embedder's convolutions on the f16 matrix cores with split operands (csrc/resnet.hip: conv_split_k; on by default): three
+        """the embedder's convolutions on the f16 matrix cores with split operands (csrc/resnet.hip: conv_tile_k with ConvSplit; on by default): three
         f16 products of scaled hi / lo halves per product, descriptors within the bound of DESIGN.md section 4; a face whose activations
         leave the f16 range is embedded again on the exact fp32 kernels.  off: the exact kernels only"""
         check(self._l.pvf_embedder_split(self._h, 1 if on else 0))

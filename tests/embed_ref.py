@@ -135,7 +135,7 @@ def layer_fp32(x, w, bias, g, beta, stride=1, pad=1, skip=None, skip_mode=0, out
 
 
 def layer_split(x, w, bias, g, beta, stride=1, pad=1, skip=None, skip_mode=0, out_hw=None, fault=None):
-    """the same layer as conv_split_k intends it: hi.hi + hi.lo + lo.hi of the f16 halves of 2^8 x and 2^w_exp w, fp32 accumulation, the
+    """the same layer as conv_tile_k<.., ConvSplit> intends it: hi.hi + hi.lo + lo.hi of the f16 halves of 2^8 x and 2^w_exp w, fp32 accumulation, the
     exact power-of-two scale back, the fp32 epilogue"""
     z, _, _ = _layer(x, w, bias, g, beta, stride, pad, skip, skip_mode, out_hw, "split", fault)
     return _nhwc(F.relu(z)).astype(np.float64)
@@ -201,7 +201,7 @@ def layer_specs(params, units):
 
 
 def is_split_layer(w):
-    """whether the product runs this layer on conv_split_k when the split path is on (everything but the first layer and the 32 -> 32 stage)"""
+    """whether the product runs this layer on conv_tile_k<.., ConvSplit> when the split path is on (everything but the first layer and the 32 -> 32 stage)"""
     return not (w.shape[0] == 32 and w.shape[1] in (3, 32))
 
 

@@ -1,4 +1,4 @@
-"""CPU restatement of the embedder's split path (csrc/resnet.hip: conv_split_k, conv_wsplit_k) on the synthetic embedder, the two chips of
+"""CPU restatement of the embedder's split path (csrc/resnet.hip: conv_tile_k with ConvSplit, conv_wsplit_k) on the synthetic embedder, the two chips of
 tests/golden/hotpath_small.npz and two random-byte chips: every convolution outside the 32-channel stage as hi.hi + hi.lo + lo.hi of f16
 halves of the scaled operands (activations x 2^8, weights x 2^w_exp with the largest |w| in [2^14, 2^15)), products and sums in f64 so
 that only the split's error is measured; the first layer and the 32-channel stage stay fp32 as in the kernels.  Descriptors are

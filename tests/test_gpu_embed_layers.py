@@ -2,11 +2,13 @@
 single layers at the shapes where such kernels go wrong (pvf_debug_conv), each judged ALONE -- the reference gets the GPU's own input of
 that layer -- under the two criteria of tests/embed_ref.py: A, a derived per-element bound; B, the layer's RMS error against f64 within
 4 x that of a CPU restatement of the same arithmetic on the same input.  tests/test_embed_layer_criteria.py shows on the CPU that the
-criteria see ten kinds of defect.  Kernels reached: stem_conv_k, maxpool3s2_k, conv3x3_c32_k, conv_mfma_k<4,1> / <2,2>,
-conv_split_k<4,1> / <2,2>, conv_wsplit_k, conv_frag_k, head_k."""
+criteria see ten kinds of defect.  Kernels reached: stem_conv_k, maxpool3s2_k, conv3x3_c32_k, conv_tile_k<4,1> / <2,2> with
+ConvExact and with ConvSplit, conv_wsplit_k, conv_frag_k, head_k."""
+import json
 import os
 import sys
 import time
+import zlib
 
 import numpy as np
 import pytest
@@ -159,7 +161,7 @@ def sweep_cases():
         cases.append(("%s-B%d-%dx%d-%d-%d" % (tag, d["B"], d["H"], d["W"], d["cin"], d["cout"]), d))
 
     # output maps of 1 .. 1225 pixels; M = B OH OW below one row tile, one tile and a bit, and with a prime number of faces.
-    # Row tiles: 128 (Cout a multiple of 64: conv_*_k<2,2>), 256 (Cout 32: <4,1>)
+    # Row tiles: 128 (Cout a multiple of 64: conv_tile_k<2,2>), 256 (Cout 32: <4,1>)
     for side in (1, 2, 3, 4, 8, 17, 35):
         hw = side * side
         for cout, tile in ((64, 128), (32, 256)):
@@ -208,7 +210,8 @@ def sweep_cases():
 SWEEP = sweep_cases()
 
 
-def run_case(ctx, d, split, seed):
+def case_inputs(d, seed):
+    """a case's tensors: (x, w, bias, gamma, beta), debug_conv's keywords"""
     rng = np.random.default_rng(seed)
     x = relu_like(rng, (d["B"], d["H"], d["W"], d["cin"]))
     w, bias, g, bt = layer_params(rng, d["cin"], d["cout"], 3, d["gamma"], d["beta"])
@@ -219,6 +222,11 @@ def run_case(ctx, d, split, seed):
     elif d["skip"] != "none":
         _, xh, xw, xc = d["skip"]
         kw.update(skip=relu_like(rng, (d["B"], xh, xw, xc)), skip_mode=2)
+    return (x, w, bias, g, bt), kw
+
+
+def run_case(ctx, d, split, seed):
+    (x, w, bias, g, bt), kw = case_inputs(d, seed)
     y, flags = ctx.debug_conv(x, w, bias, g, bt, split=split, force_generic=d["generic"], **kw)
     r = R.layer(x, w, bias, g, bt, **kw)
     assert y.shape == r["y"].shape
@@ -227,6 +235,17 @@ def run_case(ctx, d, split, seed):
     use_split = split and not own
     cpu = (R.layer_split if use_split else R.layer_fp32)(x, w, bias, g, bt, **kw)
     return R.judge(y, r, cpu, use_split), flags
+
+
+def sweep_crcs(ctx, split):
+    """"<k>-<case id>" (five ids occur twice) -> [crc32 of the output's bytes, crc32 of the flags' bytes] (hex) over SWEEP, with
+    test_shape_sweep's inputs"""
+    out = {}
+    for k, (cid, d) in enumerate(SWEEP):
+        par, kw = case_inputs(d, 1000 + k)
+        y, flags = ctx.debug_conv(*par, split=split, force_generic=d["generic"], **kw)
+        out["%03d-%s" % (k, cid)] = ["%08x" % zlib.crc32(y.tobytes()), "%08x" % zlib.crc32(flags.tobytes())]
+    return out
 
 
 @pytest.mark.parametrize("split", [False, True])
@@ -238,6 +257,19 @@ def test_shape_sweep(ctx, split):
         if not (j["a_ok"] and j["b_ok"]) or flags.any():
             bad.append((cid, j, flags.nonzero()))
     assert not bad, bad
+
+
+@pytest.mark.parametrize("split", [False, True])
+def test_sweep_bits_are_the_parents(ctx, split):
+    """every bit the sweep's layers write, against tests/golden/conv_sweep_crc32.json: recorded once on the MI355X from the commit its
+    _meta entry names, with these inputs (the generator's stream belongs to the numpy version named there)"""
+    with open(os.path.join(ROOT, "tests", "golden", "conv_sweep_crc32.json")) as f:
+        golden = json.load(f)
+    want = golden["split" if split else "exact"]
+    got = sweep_crcs(ctx, split)
+    assert sorted(want) == sorted(got)
+    differ = [key for key in sorted(got) if got[key] != want[key]]
+    assert not differ, (golden["_meta"], "numpy here: " + np.__version__, differ)
 
 
 def test_sweep_covers_what_it_says():

@@ -1,4 +1,4 @@
-"""The embedder's split path (csrc/resnet.hip: conv_split_k, the default) against its exact fp32 kernels on the same chips: the error
+"""The embedder's split path (csrc/resnet.hip: conv_tile_k with ConvSplit, the default) against its exact fp32 kernels on the same chips: the error
 bound, batch independence, the range guard with its per-face exact fallback, and the switch."""
 import os
 import sys

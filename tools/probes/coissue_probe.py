@@ -1,7 +1,7 @@
 """can the MFMA-bound embedder run INSIDE the VALU-bound pyramid kernels (designed pairing, not two streams and hope)?
 Two contexts on one device, two Python threads:
   A  the image pyramids of a 125-frame 1080p batch (resize_rows_k x 20, the detector stream), `reps` times
-  B  the embedding of 4096 chips (stem + conv3x3_c32_k + conv_mfma_k ..., the main stream), `reps` times
+  B  the embedding of 4096 chips (stem + conv3x3_c32_k + conv_tile_k ..., the main stream), `reps` times
 alone and together, with the stream priorities the engine uses (embedder above the detector), equal, and reversed (pyramid above the
 embedder: six resize blocks fill a CU first and ONE embedder block fits beside them when the resize kernel is the thin variant --
 PVF_RESIZE_THIN=1: 13.3 KB of LDS per block instead of 23.5).
