@@ -317,6 +317,29 @@ int32_t pvf_cluster_upper(pvf_handle ctx, const double* U, int32_t on_device, co
                           int32_t* labels, double* merge_log, int32_t* n_merges);
 int32_t pvf_cluster_tracks(pvf_handle ctx, const double* X, int32_t N, int32_t dim, const int32_t* row_start,
                            int32_t T, double threshold, int32_t* labels, double* merge_log, int32_t* n_merges);
+/* ref: clustering.py:142-143  `# constraint = DoNotCooccur()` / `constraint = None`: the constraint the reference names and leaves
+ * switched off, here as siblings of the four agglomerating entries.  [EXT pyannote.algorithms, absent; PARITY UNPINNED]
+ *   extent    T x 2 float64, (start, end) of each track in seconds (first and last timestamp of its rows, clustering.py:76-77).  NULL is
+ *             refused: the entries without a constraint stay for that.  A value that is not finite, or end < start, is refused.
+ *             Tracks i != j CO-OCCUR iff  min(end_i, end_j) - max(start_i, start_j) > 1e-6  (float64, this form: a non-empty
+ *             intersection by pyannote.core's Segment rule).  A pair of clusters holding a co-occurring pair of tracks is never
+ *             merged and never stops the loop: the agglomeration ends when no mergeable pair is left or the closest mergeable pair
+ *             lies above `threshold` -- with threshold = +inf that may leave more than one cluster.  Without co-occurring tracks
+ *             the result is that of the entry without a constraint, bit for bit.
+ *   n_blocked output: the co-occurring pairs i < j.
+ *   flags     bit 0: A TEST SWITCH -- run the launch-per-merge agglomeration (otherwise used above 10 200 tracks only) whatever T, so
+ *             that path can be checked at small T; same result, slower.  Other bits must be zero. */
+int32_t pvf_cluster_dist_cooccur(pvf_handle ctx, const double* D, const int32_t* row_start, int32_t T, double threshold,
+                                 int32_t* labels, double* merge_log, int32_t* n_merges, const double* extent, int32_t* n_blocked,
+                                 int32_t flags);
+/* ref: clustering.py:142-143 */
+int32_t pvf_cluster_upper_cooccur(pvf_handle ctx, const double* U, int32_t on_device, const int32_t* row_start, int32_t T,
+                                  double threshold, int32_t* labels, double* merge_log, int32_t* n_merges, const double* extent,
+                                  int32_t* n_blocked, int32_t flags);
+/* ref: clustering.py:142-143 */
+int32_t pvf_cluster_tracks_cooccur(pvf_handle ctx, const double* X, int32_t N, int32_t dim, const int32_t* row_start, int32_t T,
+                                   double threshold, int32_t* labels, double* merge_log, int32_t* n_merges, const double* extent,
+                                   int32_t* n_blocked, int32_t flags);
 /* The in-memory path (no embedding.txt in between): the float32 descriptors as pvf_embed returned them -- `emb` is a host or a device
  * address (emb_on_device), n_src rows of 128 floats row_stride_bytes apart.  Row k of the clustering's table is
  * np.round(float64(emb[order[k]]), decimals) -- what the reference reads back from the '%.5f' text (pyannote-face.py:307-311,
@@ -327,6 +350,11 @@ int32_t pvf_cluster_tracks(pvf_handle ctx, const double* X, int32_t N, int32_t d
 int32_t pvf_cluster_tracks_f32(pvf_handle ctx, const float* emb, int64_t row_stride_bytes, int32_t n_src, int32_t emb_on_device,
                                const int32_t* order, int32_t N, int32_t decimals, const int32_t* row_start, int32_t T, int32_t metric,
                                double threshold, int32_t* labels, double* merge_log, int32_t* n_merges);
+/* ref: clustering.py:142-143  pvf_cluster_tracks_f32 with the do-not-cooccur constraint (extent, n_blocked, flags: see above) */
+int32_t pvf_cluster_tracks_f32_cooccur(pvf_handle ctx, const float* emb, int64_t row_stride_bytes, int32_t n_src, int32_t emb_on_device,
+                                       const int32_t* order, int32_t N, int32_t decimals, const int32_t* row_start, int32_t T,
+                                       int32_t metric, double threshold, int32_t* labels, double* merge_log, int32_t* n_merges,
+                                       const double* extent, int32_t* n_blocked, int32_t flags);
 int32_t pvf_pair_upper_rows_f32(pvf_handle ctx, const float* emb, int64_t row_stride_bytes, int32_t n_src, int32_t emb_on_device,
                                 const int32_t* order, int32_t N, int32_t decimals, const int32_t* row_start, int32_t T,
                                 int32_t track0, int32_t track1, double* rows_out, int32_t out_on_device);

@@ -607,6 +607,8 @@ __global__ void __launch_bounds__(1024) hac_argmin_k(HacState h)
     }
 }
 
+// CO: the do-not-cooccur form (see cooccur_stamp_k below): an entry stays +inf when either parent's is
+template <bool CO>
 __global__ void __launch_bounds__(256) hac_merge_k(HacState h)
 {
     if (h.best[3] != 0.0) return;
@@ -617,12 +619,15 @@ __global__ void __launch_bounds__(256) hac_merge_k(HacState h)
     if (k == bi) { h.dirty[bi] = 1; return; }
     if (k == bj) { h.dirty[bj] = 1; return; }
     if (!h.alive[k]) return;
-    const double v = (si * h.D[(size_t)bi * h.T + k] + sj * h.D[(size_t)bj * h.T + k]) / (si + sj);
+    const double da = h.D[(size_t)bi * h.T + k], db = h.D[(size_t)bj * h.T + k];
+    double v = (si * da + sj * db) / (si + sj);
+    if (CO) v = (da == INFINITY || db == INFINITY) ? INFINITY : v;
     h.D[(size_t)bi * h.T + k] = v;
     h.D[(size_t)k * h.T + bi] = v;
     if (k < bi) {
         const int ra = h.rarg[k];
         if (ra == bi || ra == bj) h.dirty[k] = 1;
+        else if (CO && v == INFINITY) {}                       // (a row without a mergeable column keeps the argument 0x7fffffff)
         else if (v < h.rmin[k] || (v == h.rmin[k] && bi < ra)) { h.rmin[k] = v; h.rarg[k] = bi; }
     } else if (k < bj) {
         if (h.rarg[k] == bj) h.dirty[k] = 1;
@@ -695,7 +700,12 @@ __device__ __forceinline__ void pick16(const double* wv, const int* wi, double& 
     }
 }
 
-template <int U>
+// CO (the do-not-cooccur form, clustering.py:142-143): forbidden pairs sit in D as +inf (cooccur_stamp_k).  Under average linkage that
+// is all the state the constraint needs: the size-weighted mean of two entries is +inf wherever either is, which is "the merged cluster
+// co-occurs with k iff one of its parents did".  What CO adds is that select -- the corrected quotient below would turn +inf into NaN
+// (fma(-den, inf, inf)) -- and nothing else: `v < bv` never takes a +inf entry, so a row whose columns are all forbidden keeps
+// (inf, 0x7fffffff), the argmin of such rows alone is 0x7fffffff and the loop ends there, whatever the threshold (+inf with `force`).
+template <int U, bool CO>
 __global__ void __launch_bounds__(1024) hac_persist_k(HacState h)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char hsm[];
@@ -765,11 +775,13 @@ __global__ void __launch_bounds__(1024) hac_persist_k(HacState h)
             double v = num * yrc;
             v = __builtin_fma(__builtin_fma(-den, v, num), yrc, v);
             v = __builtin_fma(__builtin_fma(-den, v, num), yrc, v);
+            if (CO) v = (a[u] == INFINITY || b[u] == INFINITY) ? INFINITY : v;
             D[(size_t)mi * T + k] = v;
             D[(size_t)k * T + mi] = v;
             if (k < mi) {
                 const int ra = rarg[k];
                 if (ra == mi || ra == mj) dlist[atomicAdd(&s_nd, 1)] = (uint16_t)k;
+                else if (CO && v == INFINITY) {}               // (equal to the +inf of a row without a mergeable column: its argument stays 0x7fffffff)
                 else if (v < rmin[k] || (v == rmin[k] && mi < ra)) { rmin[k] = v; rarg[k] = mi; }
             } else {
                 if (k < mj && rarg[k] == mj) dlist[atomicAdd(&s_nd, 1)] = (uint16_t)k;
@@ -835,16 +847,53 @@ __global__ void __launch_bounds__(1024) hac_persist_k(HacState h)
     if (tid == 0) *h.n_merges = merges;
 }
 
-int hac_dev(Ctx* c, double* d_D, const int32_t* row_start, int T, double threshold, int32_t* labels, double* merge_log)
+// The do-not-cooccur constraint (clustering.py:142-143 names it and leaves it off): tracks whose extents [start, end] intersect are two
+// people.  D[i][j] = D[j][i] = +inf for every such pair i != j, the diagonal untouched; *n_blocked += the pairs i < j.  64 x 64 tiles: a
+// thread keeps its column's extent in registers, the 64 row extents of the tile go through LDS once, D is only written (both triangles
+// are swept and the test is symmetric in i and j -- min and max commute -- so the mirror entry is written by the mirror tile, row-wise).
+__global__ void __launch_bounds__(256) cooccur_stamp_k(double* __restrict__ D, int T, const double* __restrict__ extent, int* __restrict__ n_blocked)
+{
+    __shared__ double rs[64], re[64];
+    __shared__ int cnt[4];
+    const int tid = threadIdx.x, tx = tid & 63, ty = tid >> 6;
+    const int i0 = blockIdx.y * 64, j = blockIdx.x * 64 + tx;
+    if (tid < 64 && i0 + tid < T) { rs[tid] = extent[2 * (size_t)(i0 + tid)]; re[tid] = extent[2 * (size_t)(i0 + tid) + 1]; }
+    double cs = 0.0, ce = 0.0;
+    if (j < T) { cs = extent[2 * (size_t)j]; ce = extent[2 * (size_t)j + 1]; }
+    __syncthreads();
+    int n = 0;
+    if (j < T) {
+        const int nr = min(64, T - i0);
+        for (int r = ty; r < nr; r += 4) {
+            const int i = i0 + r;
+            // the non-empty intersection by pyannote.core's rule (Segment.__bool__: longer than 1e-6), in this form exactly
+            if (i != j && fmin(re[r], ce) - fmax(rs[r], cs) > 1e-6) {
+                D[(size_t)i * T + j] = INFINITY;
+                n += i < j;
+            }
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) n += __shfl_down(n, off, 64);
+    if (tx == 0) cnt[ty] = n;
+    __syncthreads();
+    if (tid == 0 && cnt[0] + cnt[1] + cnt[2] + cnt[3] > 0) atomicAdd(n_blocked, cnt[0] + cnt[1] + cnt[2] + cnt[3]);
+}
+
+// extent: optional T x 2 float64 (start, end) per track, checked by the caller (api.hip refuses bad ones before any device work)
+// -> the constrained agglomeration (n_blocked: forbidden pairs i < j);
+// flags bit 0: the launch-per-merge path whatever T (a test switch: that path is otherwise reached above HAC_PERSIST_MAX_T only)
+int hac_dev(Ctx* c, double* d_D, const int32_t* row_start, int T, double threshold, int32_t* labels, double* merge_log,
+            const double* extent, int32_t* n_blocked, int flags)
 {
     for (int i = 0; i < T; ++i) labels[i] = i;
+    if (n_blocked) *n_blocked = 0;
     if (T < 2) return 0;
-    const size_t need = (size_t)T * (8 + 4 + 4 + 4 + 8) + 4 * 8 + (size_t)T * 4 * 8 + 64 + (size_t)(T + 1) * 4 + 512;
+    const size_t need = (size_t)T * (8 + 4 + 4 + 4 + 8) + 4 * 8 + (size_t)T * 4 * 8 + 64 + (size_t)(T + 1) * 4 + 512 + (extent ? (size_t)T * 16 + 64 : 0);
     c->s_misc.ensure(need);
     uint8_t* p = c->s_misc.as<uint8_t>();
     auto take = [&](size_t bytes) { uint8_t* q = p; p += (bytes + 63) / 64 * 64; return q; };
     // note: the bump sizes above leave slack for the 64-byte rounding
-    c->s_misc.ensure(need + 64 * 10);
+    c->s_misc.ensure(need + 64 * (extent ? 12 : 10));
     p = c->s_misc.as<uint8_t>();
     HacState h;
     h.D = d_D; h.T = T; h.threshold = threshold;
@@ -858,27 +907,51 @@ int hac_dev(Ctx* c, double* d_D, const int32_t* row_start, int T, double thresho
     h.n_merges = (int*)take(64);
     int32_t* dR = (int32_t*)take((size_t)(T + 1) * 4);
     HIP_CHECK(hipMemcpyAsync(dR, row_start, (size_t)(T + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    double* dExt = nullptr; int* dBlocked = nullptr;
+    if (extent) {
+        dExt = (double*)take((size_t)T * 16);
+        dBlocked = (int*)take(64);
+        HIP_CHECK(hipMemcpyAsync(dExt, extent, (size_t)T * 16, hipMemcpyHostToDevice, c->stream));
+        HIP_CHECK(hipMemsetAsync(dBlocked, 0, 4, c->stream));
+    }
     ProfScope ps(c, "hac");
     hipLaunchKernelGGL(hac_init_k, dim3((T + 255) / 256), dim3(256), 0, c->stream, h, dR);
+    if (extent) {
+        ProfScope pst(c, "cooccur_stamp");
+        hipLaunchKernelGGL(cooccur_stamp_k, dim3((T + 63) / 64, (T + 63) / 64), dim3(256), 0, c->stream, d_D, T, dExt, dBlocked);
+    }
     hipLaunchKernelGGL(hac_row_min_k, dim3(T), dim3(256), 0, c->stream, h, 0);
     double hbest[4];
-    if (T <= HAC_PERSIST_MAX_T) {
+    if (T <= HAC_PERSIST_MAX_T && !(flags & 1)) {
         const size_t lds = hac_persist_lds(T);           // rmin f64, rarg i32, re-scan list u16, alive bits
         static std::atomic<uint64_t> attr_on{0};          // per device (a function attribute belongs to the device it was set on)
         const uint64_t dev_bit = 1ull << (c->device & 63);
         if (!(attr_on.load() & dev_bit)) {
-            HIP_CHECK(hipFuncSetAttribute((const void*)hac_persist_k<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hac_persist_lds(1024)));
-            HIP_CHECK(hipFuncSetAttribute((const void*)hac_persist_k<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hac_persist_lds(3072)));
-            HIP_CHECK(hipFuncSetAttribute((const void*)hac_persist_k<10>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hac_persist_lds(HAC_PERSIST_MAX_T)));
+            HIP_CHECK(hipFuncSetAttribute((const void*)hac_persist_k<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hac_persist_lds(1024)));
+            HIP_CHECK(hipFuncSetAttribute((const void*)hac_persist_k<3, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hac_persist_lds(3072)));
+            HIP_CHECK(hipFuncSetAttribute((const void*)hac_persist_k<10, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hac_persist_lds(HAC_PERSIST_MAX_T)));
             attr_on.fetch_or(dev_bit);
         }
-        if (T <= 1024) hipLaunchKernelGGL(hac_persist_k<1>, dim3(1), dim3(1024), lds, c->stream, h);
-        else if (T <= 3072) hipLaunchKernelGGL(hac_persist_k<3>, dim3(1), dim3(1024), lds, c->stream, h);
-        else hipLaunchKernelGGL(hac_persist_k<10>, dim3(1), dim3(1024), lds, c->stream, h);
+        static std::atomic<uint64_t> attr_co_on{0};       // the constrained instantiations: on their first use
+        if (extent && !(attr_co_on.load() & dev_bit)) {
+            HIP_CHECK(hipFuncSetAttribute((const void*)hac_persist_k<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hac_persist_lds(1024)));
+            HIP_CHECK(hipFuncSetAttribute((const void*)hac_persist_k<3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hac_persist_lds(3072)));
+            HIP_CHECK(hipFuncSetAttribute((const void*)hac_persist_k<10, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hac_persist_lds(HAC_PERSIST_MAX_T)));
+            attr_co_on.fetch_or(dev_bit);
+        }
+        if (extent) {
+            if (T <= 1024) hipLaunchKernelGGL((hac_persist_k<1, true>), dim3(1), dim3(1024), lds, c->stream, h);
+            else if (T <= 3072) hipLaunchKernelGGL((hac_persist_k<3, true>), dim3(1), dim3(1024), lds, c->stream, h);
+            else hipLaunchKernelGGL((hac_persist_k<10, true>), dim3(1), dim3(1024), lds, c->stream, h);
+        }
+        else if (T <= 1024) hipLaunchKernelGGL((hac_persist_k<1, false>), dim3(1), dim3(1024), lds, c->stream, h);
+        else if (T <= 3072) hipLaunchKernelGGL((hac_persist_k<3, false>), dim3(1), dim3(1024), lds, c->stream, h);
+        else hipLaunchKernelGGL((hac_persist_k<10, false>), dim3(1), dim3(1024), lds, c->stream, h);
     } else
     for (int it = 0; it < T - 1; ++it) {
         hipLaunchKernelGGL(hac_argmin_k, dim3(1), dim3(1024), 0, c->stream, h);
-        hipLaunchKernelGGL(hac_merge_k, dim3((T + 255) / 256), dim3(256), 0, c->stream, h);
+        if (extent) hipLaunchKernelGGL(hac_merge_k<true>, dim3((T + 255) / 256), dim3(256), 0, c->stream, h);
+        else hipLaunchKernelGGL(hac_merge_k<false>, dim3((T + 255) / 256), dim3(256), 0, c->stream, h);
         hipLaunchKernelGGL(hac_finish_merge_k, dim3(1), dim3(1), 0, c->stream, h);
         hipLaunchKernelGGL(hac_row_min_k, dim3(T), dim3(256), 0, c->stream, h, 1);
         if ((it & 63) == 63) {
@@ -890,6 +963,7 @@ int hac_dev(Ctx* c, double* d_D, const int32_t* row_start, int T, double thresho
     HIP_CHECK(hipGetLastError());
     int n = 0;
     HIP_CHECK(hipMemcpyAsync(&n, h.n_merges, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (extent && n_blocked) HIP_CHECK(hipMemcpyAsync(n_blocked, dBlocked, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIP_CHECK(hipStreamSynchronize(c->stream));
     std::vector<double> log((size_t)std::max(n, 1) * 4);
     if (n > 0) {

@@ -431,4 +431,5 @@ struct PairOutput { double* out = nullptr; bool on_device = false; bool compact 
 void pair_mean_dist_dev(Ctx* c, const PairInput& in, int N, int dim, const int32_t* row_start, int T, const PairOutput& out, double** d_D_keep,
                         int t0, int t1, int metric, bool mirror);
 void mirror_upper_dev(Ctx* c, double* dD, int T);
-int hac_dev(Ctx* c, double* d_D, const int32_t* row_start, int T, double threshold, int32_t* labels, double* merge_log);
+int hac_dev(Ctx* c, double* d_D, const int32_t* row_start, int T, double threshold, int32_t* labels, double* merge_log,
+            const double* extent = nullptr, int32_t* n_blocked = nullptr, int flags = 0);

@@ -108,6 +108,12 @@ _SIGS = {
     "pvf_cluster_tracks": (C.c_int32, [H, P, C.c_int32, C.c_int32, P, C.c_int32, C.c_double, P, P, P]),
     "pvf_cluster_upper": (C.c_int32, [H, P, C.c_int32, P, C.c_int32, C.c_double, P, P, P]),
     "pvf_cluster_tracks_f32": (C.c_int32, [H, P, C.c_int64, C.c_int32, C.c_int32, P, C.c_int32, C.c_int32, P, C.c_int32, C.c_int32, C.c_double, P, P, P]),
+    # the do-not-cooccur siblings (clustering.py:142-143): the same arguments + extent, n_blocked, flags
+    "pvf_cluster_dist_cooccur": (C.c_int32, [H, P, P, C.c_int32, C.c_double, P, P, P, P, P, C.c_int32]),
+    "pvf_cluster_tracks_cooccur": (C.c_int32, [H, P, C.c_int32, C.c_int32, P, C.c_int32, C.c_double, P, P, P, P, P, C.c_int32]),
+    "pvf_cluster_upper_cooccur": (C.c_int32, [H, P, C.c_int32, P, C.c_int32, C.c_double, P, P, P, P, P, C.c_int32]),
+    "pvf_cluster_tracks_f32_cooccur": (C.c_int32, [H, P, C.c_int64, C.c_int32, C.c_int32, P, C.c_int32, C.c_int32, P, C.c_int32, C.c_int32, C.c_double, P, P, P,
+                                                   P, P, C.c_int32]),
     "pvf_pair_upper_rows_f32": (C.c_int32, [H, P, C.c_int64, C.c_int32, C.c_int32, P, C.c_int32, C.c_int32, P, C.c_int32, C.c_int32, C.c_int32, P, C.c_int32]),
     "pvf_format_rows": (C.c_int32, [P, P, P, C.c_int64, C.c_int32, C.c_int32, P, C.c_int64, P]),
     "pvf_round_rows": (C.c_int32, [P, C.c_int64, C.c_int32, P]),

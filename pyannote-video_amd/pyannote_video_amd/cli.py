@@ -250,13 +250,13 @@ def extract(video, landmark_model, embedding_model, tracking, landmark_output, e
 
 def process(video, shot, landmark_model, embedding_model, tracking_output, landmark_output, embedding_output, label_output=None,
             detect_min_size=0.0, detect_every=0.0, track_min_overlap_ratio=MIN_OVERLAP_RATIO, track_min_confidence=MIN_CONFIDENCE,
-            track_max_gap=MAX_GAP, threshold=0.6, ctx=None):
+            track_max_gap=MAX_GAP, threshold=0.6, ctx=None, do_not_cooccur=False):
     """`track` + `extract` (+ `cluster`) in ONE pass over the video -- one decode, one upload per frame; the reference needs two decodes
     (pyannote-face.py:261 and :287).  Writes the same three files as the separate verbs, line for line (the faces of one frame in the
     order pandas' sort of the complete track table gives them: formats.file_order), plus the `identifier label` file of `cluster`."""
     pipe = _pipeline(video, ctx, landmark_model, embedding_model, detect_min_size=detect_min_size, detect_every=detect_every,
                      track_min_overlap_ratio=track_min_overlap_ratio, track_min_confidence=track_min_confidence, track_max_gap=track_max_gap,
-                     threshold=threshold)
+                     threshold=threshold, constraint="cooccur" if do_not_cooccur else None)
     shots = load_shots(shot) if isinstance(shot, str) else shot
     state = {"next": 0}
     with open(tracking_output, 'w') as foutput:
@@ -285,11 +285,12 @@ def _times(video):
     return [(i / video.frame_rate, None) for i in range(n)]
 
 
-def cluster(embeddings, output, threshold=0.6, force=False, metric="euclidean", ctx=None):
+def cluster(embeddings, output, threshold=0.6, force=False, metric="euclidean", ctx=None, do_not_cooccur=False):
     """FaceClustering on an embedding file (face/clustering.py:130-134) -> `identifier label` lines for `demo --label`.
-    Tracks that take no part in the clustering (a single timestamp: clustering.py:78-79) keep their own identifier as label."""
+    Tracks that take no part in the clustering (a single timestamp: clustering.py:78-79) keep their own identifier as label.
+    do_not_cooccur: tracks whose extents intersect never get the same label (clustering.py:142-143, FaceClustering(constraint='cooccur'))."""
     from .clustering import FaceClustering
-    clustering = FaceClustering(threshold=threshold, force=force, metric=metric, ctx=ctx)
+    clustering = FaceClustering(threshold=threshold, force=force, metric=metric, ctx=ctx, constraint="cooccur" if do_not_cooccur else None)
     starting_point, features = clustering.model.preprocess(embeddings)
     result = clustering(starting_point, features=features)
     label = {int(track): int(lab) for _, track, lab in result.itertracks(yield_label=True)}
@@ -450,6 +451,7 @@ def _parser():
     pr.add_argument("--min-confidence", type=float, default=MIN_CONFIDENCE)
     pr.add_argument("--max-gap", type=float, default=MAX_GAP)
     pr.add_argument("--threshold", type=float, default=0.6)
+    pr.add_argument("--do-not-cooccur", action="store_true", help="tracks on screen at the same time never share a label")
     s = sub.add_parser("shot")
     s.add_argument("video"); s.add_argument("output")
     s.add_argument("--height", type=int, default=50, help="height of the images the optical flow runs on (reference default 50: one pyramid level; "
@@ -465,6 +467,8 @@ def _parser():
     c.add_argument("--threshold", type=float, default=0.6)
     c.add_argument("--force", action="store_true")
     c.add_argument("--metric", choices=("euclidean", "cosine"), default="euclidean")
+    c.add_argument("--do-not-cooccur", action="store_true", help="tracks on screen at the same time never share a label "
+                   "(the constraint face/clustering.py:142 names and leaves off)")
     d = sub.add_parser("demo", help="the video with tracks, labels and landmarks drawn on it, as YUV4MPEG2")
     d.add_argument("video"); d.add_argument("tracking"); d.add_argument("output", help="a .y4m path, or - for stdout")
     d.add_argument("--height", type=int, default=400, help="height of the output frames; the width keeps the aspect")
@@ -506,7 +510,7 @@ def main(argv=None):
     elif a.verb == "process":
         res = process(video(), a.shot, a.landmark_model, a.embedding_model, a.tracking, a.landmarks, a.embeddings, a.labels,
                 detect_min_size=a.min_size, detect_every=a.every, track_min_overlap_ratio=a.min_overlap,
-                track_min_confidence=a.min_confidence, track_max_gap=a.max_gap, threshold=a.threshold, ctx=ctx)
+                track_min_confidence=a.min_confidence, track_max_gap=a.max_gap, threshold=a.threshold, ctx=ctx, do_not_cooccur=a.do_not_cooccur)
     elif a.verb == "shot":
         shot(video(), a.output, height=a.height, window=a.window, threshold=a.threshold, ctx=ctx)
     elif a.verb == "thread":
@@ -519,7 +523,7 @@ def main(argv=None):
     elif a.verb == "extract":
         extract(video(), a.landmark_model, a.embedding_model, a.tracking, a.landmarks, a.embeddings, ctx=ctx)
     else:
-        cluster(a.embeddings, a.labels, threshold=a.threshold, force=a.force, metric=a.metric, ctx=ctx)
+        cluster(a.embeddings, a.labels, threshold=a.threshold, force=a.force, metric=a.metric, ctx=ctx, do_not_cooccur=a.do_not_cooccur)
     if a.metrics:
         from . import runtime
         m = {"verb": a.verb, "seconds": round(time.perf_counter() - t_begin, 4)}

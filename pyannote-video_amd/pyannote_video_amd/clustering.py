@@ -151,13 +151,28 @@ class FaceClustering(object):
                                    agglomeration runs on to a single cluster so that `history` holds the complete dendrogram, while
                                    the result is still the partition at which the threshold was crossed.
     metric : 'euclidean' (the reference, clustering.py:101) or 'cosine' (named by BASELINE.json's north_star; 1 - cos of the pair)
+    constraint : None (the reference: clustering.py:143 `constraint = None`) or 'cooccur' -- the one it names and leaves switched off
+                                   (clustering.py:142 `# constraint = DoNotCooccur()`).  [EXT pyannote.algorithms, PARITY UNPINNED]:
+                                   two tracks that are on screen at the same time are two people.  A track's extent is the segment
+                                   `preprocess` gives it (first and last timestamp of its rows); tracks co-occur when their extents
+                                   intersect in more than pyannote.core's precision, min(end) - max(start) > 1e-6.  A pair of
+                                   clusters that holds a co-occurring pair of tracks is never merged and never stops the loop; with
+                                   `force` the agglomeration runs until no mergeable pair is left, which may be more than one
+                                   cluster.  `n_blocked` (beside `history`) is the number of co-occurring track pairs of the last
+                                   call.  The constraint lives inside the agglomeration kernel ("Do-not-cooccur"); the
+                                   hook-driven form -- an outside driver calling `model`'s four hooks -- is out of scope: `_Model`
+                                   knows nothing of it.
     """
 
-    def __init__(self, threshold=0.6, force=False, logger=None, ctx=None, metric="euclidean"):
+    def __init__(self, threshold=0.6, force=False, logger=None, ctx=None, metric="euclidean", constraint=None):
         if metric not in ("euclidean", "cosine"):
             raise ValueError("metric must be 'euclidean' or 'cosine'")
+        if constraint not in (None, "cooccur"):
+            raise ValueError("constraint must be None or 'cooccur'")
         self.force = bool(force)
         self.metric = metric
+        self.constraint = constraint
+        self.n_blocked = None  # co-occurring track pairs of the last constrained call
         self.threshold = threshold
         self.model = _Model(ctx)
         self.ctx = ctx
@@ -165,8 +180,18 @@ class FaceClustering(object):
         self.history = None
         self.shard = None      # dist.DistanceShard when the pairwise distances are split over the ranks of a job
 
-    def cluster_arrays(self, track_ids, row_track, X):
-        """labels for `track_ids` (sorted unique ints) given per-row track ids; X float64 [N, dim]"""
+    def _agglomerate(self, obj, name, args, extent, **kw):
+        """(labels, log) of obj.<name>(*args, **kw), or of its `_cooccur` sibling with the extents (n_blocked kept) when the constraint is on"""
+        if extent is None:
+            return getattr(obj, name)(*args, **kw)
+        labels, log, self.n_blocked = getattr(obj, name + "_cooccur")(*args, extent=extent, **kw)
+        return labels, log
+
+    def cluster_arrays(self, track_ids, row_track, X, time=None):
+        """labels for `track_ids` (sorted unique ints) given per-row track ids; X float64 [N, dim]; time: the rows' timestamps, which
+        the 'cooccur' constraint needs (a track's extent = its smallest and largest one, clustering.py:76-77)"""
+        if self.constraint is not None and time is None:
+            raise ValueError("constraint='cooccur' needs the rows' timestamps (time=)")
         ctx = self.ctx or runtime.default_context()
         order = np.argsort(row_track, kind="stable")
         keep = np.isin(row_track[order], track_ids)
@@ -177,17 +202,23 @@ class FaceClustering(object):
         counts = np.searchsorted(rt, track_ids, side="right") - np.searchsorted(rt, track_ids, side="left")     # rt is sorted (stable argsort above)
         row_start = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
         cut = float("inf") if self.force else self.threshold
+        extent = None
+        if self.constraint is not None:
+            if (counts <= 0).any():
+                raise ValueError("constraint='cooccur': a track without rows has no extent")
+            tm = np.asarray(time, np.float64)[rows]
+            extent = np.stack([np.minimum.reduceat(tm, row_start[:-1]), np.maximum.reduceat(tm, row_start[:-1])], axis=1)
         if self.metric == "cosine":
             D = ctx.pair_mean_dist(Xs, row_start, metric=1)
-            labels, log = ctx.cluster_dist(D, row_start, cut)
+            labels, log = self._agglomerate(ctx, "cluster_dist", (D, row_start, cut), extent)
         elif self.shard is None:
-            labels, log = ctx.cluster_tracks(Xs, row_start, cut)
+            labels, log = self._agglomerate(ctx, "cluster_tracks", (Xs, row_start, cut), extent)
         else:
             # several GPUs, every one holding all rows: each computes the distance-matrix rows of its share of the tracks
             # (balanced by row count), the rows are exchanged, and every rank agglomerates the same complete matrix
             t0, t1 = self.shard.track_range(row_start)
             U = self.shard.assemble(ctx.pair_upper_rows(Xs, row_start, t0, t1)[t0:t1], row_start)
-            labels, log = ctx.cluster_upper(U, row_start, cut)
+            labels, log = self._agglomerate(ctx, "cluster_upper", (U, row_start, cut), extent)
         self.history = [(int(track_ids[int(a)]), int(track_ids[int(b)]), float(d)) for a, b, d, _ in log]
         if self.force:
             # complete dendrogram in `history`; the partition returned is the one before the first merge above the threshold
@@ -201,21 +232,25 @@ class FaceClustering(object):
 
     # ---- the in-memory path: float32 descriptors straight from the embedder, no float64 table on the host ---------------------------
     @staticmethod
-    def plan_rows(time, track):
+    def plan_rows(time, track, extents=False):
         """Index work of `preprocess` + `cluster_arrays` for rows given as (time, track) columns: -> (track ids that take part, sorted;
         order = the rows of those tracks in (track, time) order -- clustering.py:72 sort_values(by=['track', 'time']); row_start).
-        Tracks whose extent is an empty segment (one timestamp) are left out like the reference leaves them out (clustering.py:76-79)."""
+        Tracks whose extent is an empty segment (one timestamp) are left out like the reference leaves them out (clustering.py:76-79).
+        extents=True: also the (start, end) of those tracks, float64 [T, 2] -- what the 'cooccur' constraint works on."""
         time = np.asarray(time, np.float64)
         track = np.asarray(track, np.int64)
         order = np.lexsort((time, track))
         tr, tm = track[order], time[order]
         ids, first, count = np.unique(tr, return_index=True, return_counts=True)
         # Segment(t_min, t_max) is empty when its duration is not above pyannote.core's precision (1e-6): _core.Segment.__bool__
+        ext = np.stack([tm[first], tm[first + count - 1]], axis=1) if len(ids) else np.zeros((0, 2))
         keep = (tm[first + count - 1] - tm[first]) > 1e-6
         if not keep.all():
             order = order[np.repeat(keep, count)]
-            ids, count = ids[keep], count[keep]
+            ids, count, ext = ids[keep], count[keep], ext[keep]
         row_start = np.concatenate([[0], np.cumsum(count)]).astype(np.int32)
+        if extents:
+            return ids, order.astype(np.int32), row_start, np.ascontiguousarray(ext, np.float64)
         return ids, order.astype(np.int32), row_start
 
     def cluster_rows(self, time, track, emb, decimals=5, src_index=None):
@@ -224,17 +259,21 @@ class FaceClustering(object):
         preprocess((time, track, round(emb, 5))) followed by __call__ returns, with the rounding, the (track, time) gather, the pair
         means and the agglomeration on the device (pvf_cluster_tracks_f32; the split form over the ranks of a job when `shard` is set)."""
         ctx = self.ctx or runtime.default_context()
-        ids, order, row_start = self.plan_rows(time, track)
+        ids, order, row_start, extent = self.plan_rows(time, track, extents=True)
+        if self.constraint is None:
+            extent = None
         if len(ids) == 0:
             self.history = []
+            self.n_blocked = 0 if self.constraint is not None else None
             return {}
         if src_index is not None:          # row k of (time, track) is emb[src_index[k]] (rows that were reordered without being moved)
             order = np.asarray(src_index)[order].astype(np.int32)
         cut = float("inf") if self.force else self.threshold
         if self.shard is None or self.metric == "cosine":
-            labels, log = ctx.cluster_tracks_f32(emb, order, row_start, cut, decimals=decimals, metric=1 if self.metric == "cosine" else 0)
+            labels, log = self._agglomerate(ctx, "cluster_tracks_f32", (emb, order, row_start, cut), extent, decimals=decimals,
+                                            metric=1 if self.metric == "cosine" else 0)
         else:
-            labels, log = self.shard.cluster(ctx, emb, order, row_start, cut, decimals)
+            labels, log = self._agglomerate(self.shard, "cluster", (ctx, emb, order, row_start, cut, decimals), extent)
         return self._labels_of(ids, labels, log)
 
     def _labels_of(self, ids, labels, log):
@@ -251,5 +290,5 @@ class FaceClustering(object):
         tracks = sorted(set(label for _, _, label in starting_point.itertracks(yield_label=True)))
         if not tracks:
             return starting_point.copy()
-        labels = self.cluster_arrays(np.asarray(tracks, np.int64), features.track, features.X)
+        labels = self.cluster_arrays(np.asarray(tracks, np.int64), features.track, features.X, time=features.time)
         return starting_point.rename_labels(dict(zip(tracks, labels)))

@@ -428,9 +428,9 @@ class DistanceShard(object):
         assert counts == [cuts[r + 1] - cuts[r] for r in range(self.world)] and int(G.shape[0]) == T
         return G.cpu().numpy().view(np.float64).reshape(T, T)
 
-    def cluster(self, ctx, emb, order, row_start, cut, decimals=5):
-        """the split clustering with everything in HBM: this rank's rows of the upper triangle from the float32 rows (table made on the
-        device), all-gather device to device, mirror + agglomeration -> (labels, merge log)"""
+    def _upper(self, ctx, emb, order, row_start, decimals):
+        """this rank's rows of the upper triangle from the float32 rows (table made on the device), all-gathered: the assembled T x T
+        upper triangle, numpy for rows in host memory, DeviceRows (device to device) otherwise"""
         import torch
         from .runtime import DeviceRows
         T = len(row_start) - 1
@@ -438,8 +438,7 @@ class DistanceShard(object):
         ex = exchange()
         if not isinstance(emb, DeviceRows):
             # rows in host memory (a CPU-resident gather): the host form
-            U = self.assemble(ctx.pair_upper_rows_f32(emb, order, row_start, t0, t1, decimals=decimals), row_start)
-            return ctx.cluster_upper(U, row_start, cut)
+            return self.assemble(ctx.pair_upper_rows_f32(emb, order, row_start, t0, t1, decimals=decimals), row_start)
         dev = emb.keep.device if emb.keep is not None else torch.device("cuda", torch.cuda.current_device())
         mine = torch.empty((max(t1 - t0, 0), T), dtype=torch.float64, device=dev)
         if t1 > t0:
@@ -447,7 +446,16 @@ class DistanceShard(object):
         G, counts = ex.allgather(mine.view(torch.uint8).reshape(-1, T * 8))
         cuts = self.bounds(row_start)
         assert counts == [cuts[r + 1] - cuts[r] for r in range(self.world)] and int(G.shape[0]) == T
-        return ctx.cluster_upper(DeviceRows(G.data_ptr(), T, T * 8, keep=G), row_start, cut)
+        return DeviceRows(G.data_ptr(), T, T * 8, keep=G)
+
+    def cluster(self, ctx, emb, order, row_start, cut, decimals=5):
+        """the split clustering with everything in HBM: upper-triangle rows, all-gather, mirror + agglomeration -> (labels, merge log)"""
+        return ctx.cluster_upper(self._upper(ctx, emb, order, row_start, decimals), row_start, cut)
+
+    def cluster_cooccur(self, ctx, emb, order, row_start, cut, decimals=5, *, extent):
+        """the same with the do-not-cooccur constraint (extent: float64 [T, 2]): every rank stamps the assembled matrix itself
+        (pvf_cluster_upper_cooccur), so all ranks still agglomerate one matrix -> (labels, merge log, n_blocked)"""
+        return ctx.cluster_upper_cooccur(self._upper(ctx, emb, order, row_start, decimals), row_start, cut, extent)
 
 
 def global_cluster(clustering, face_T, face_id, X):

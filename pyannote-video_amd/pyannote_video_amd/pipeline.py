@@ -58,7 +58,7 @@ class FacePipeline(object):
     def __init__(self, ctx, landmarks, embedding, detect_min_size=0.0, detect_every=0.0,
                  track_min_overlap_ratio=CLI_MIN_OVERLAP_RATIO, track_min_confidence=CLI_MIN_CONFIDENCE,
                  track_max_gap=CLI_MAX_GAP, threshold=0.6, detect_batch_size=8, overlap=True,
-                 speculate_limit=8192, speculate_window=4096):
+                 speculate_limit=8192, speculate_window=4096, constraint=None):
         self.ctx = ctx
         # overlap=True: ONE host thread feeds the GPU with large batches in a fixed order -- detect shot k, bulk tracker work of
         # shot k, align + embed the faces of shot k-1 -- while the caller's thread runs the host state machine (association,
@@ -76,7 +76,9 @@ class FacePipeline(object):
                                      track_min_confidence=track_min_confidence,
                                      track_min_overlap_ratio=track_min_overlap_ratio,
                                      track_max_gap=track_max_gap, ctx=ctx, detect_batch_size=detect_batch_size)
-        self.clustering = FaceClustering(threshold=threshold, ctx=ctx)
+        # constraint='cooccur': tracks on screen at the same time never share a label (clustering.py:142-143; FaceClustering); what run(),
+        # run_stream() and run_many() cluster with, from the (time, track) columns the engine's extraction hands back
+        self.clustering = FaceClustering(threshold=threshold, ctx=ctx, constraint=constraint)
         self.detect_every = detect_every
         self.return_table = True       # results carry "X", the float64 table of the clustering (a host pass over all descriptors)
         self.detect_min_size = detect_min_size

@@ -874,15 +874,37 @@ class Context(object):
         check(self._l.pvf_pair_mean_dist_metric(self._h, ptr(X), X.shape[0], X.shape[1], ptr(rs), T, int(metric), ptr(D)))
         return D
 
-    def cluster_tracks(self, X, row_start, threshold):
+    # The four agglomerating calls have a `_cooccur` sibling that takes `extent` (float64 [T, 2]: start and end of every track, seconds):
+    # the do-not-cooccur constraint (clustering.py:142-143; pvf_cluster_*_cooccur) -- tracks whose extents intersect never share a
+    # cluster.  They return (labels, merge log, n_blocked = the co-occurring pairs); `flags` bit 0 is the library's test switch
+    # (launch-per-merge path).
+    @staticmethod
+    def _extent(extent, T):
+        e = np.ascontiguousarray(extent, np.float64)
+        if e.shape != (T, 2):
+            raise ValueError("extent: float64 [T, 2] (start, end) is expected")
+        return e
+
+    def _cluster_tracks(self, X, row_start, threshold, extent=None, flags=0):
         X = np.ascontiguousarray(X, np.float64)
         rs = np.ascontiguousarray(row_start, np.int32)
         T = len(rs) - 1
         labels = np.zeros(T, np.int32)
         log = np.zeros((max(T - 1, 1), 4), np.float64)
-        n = C.c_int32(0)
-        check(self._l.pvf_cluster_tracks(self._h, ptr(X), X.shape[0], X.shape[1], ptr(rs), T, float(threshold), ptr(labels), ptr(log), C.byref(n)))
-        return labels, log[:n.value]
+        n, nb = C.c_int32(0), C.c_int32(0)
+        if extent is not None:
+            e = self._extent(extent, T)
+            check(self._l.pvf_cluster_tracks_cooccur(self._h, ptr(X), X.shape[0], X.shape[1], ptr(rs), T, float(threshold), ptr(labels), ptr(log),
+                                                     C.byref(n), ptr(e), C.byref(nb), int(flags)))
+        else:
+            check(self._l.pvf_cluster_tracks(self._h, ptr(X), X.shape[0], X.shape[1], ptr(rs), T, float(threshold), ptr(labels), ptr(log), C.byref(n)))
+        return labels, log[:n.value], nb.value
+
+    def cluster_tracks(self, X, row_start, threshold):
+        return self._cluster_tracks(X, row_start, threshold)[:2]
+
+    def cluster_tracks_cooccur(self, X, row_start, threshold, extent, flags=0):
+        return self._cluster_tracks(X, row_start, threshold, self._extent(extent, len(row_start) - 1), flags)
 
     @staticmethod
     def _f32_rows(emb):
@@ -894,7 +916,7 @@ class Context(object):
             a = np.ascontiguousarray(a, np.float32).reshape(-1, 128)
         return ptr(a), int(a.strides[0]) if len(a) else 512, len(a), 0, a
 
-    def cluster_tracks_f32(self, emb, order, row_start, threshold, decimals=5, metric=0):
+    def _cluster_tracks_f32(self, emb, order, row_start, threshold, decimals=5, metric=0, extent=None, flags=0):
         """the in-memory clustering (pvf_cluster_tracks_f32): float32 descriptors (numpy [n, 128] or DeviceRows), rows of the table =
         round(emb[order], decimals) made on the device, upper-triangle pair means, mirror, agglomeration -> (labels, merge log)"""
         p, stride, n_src, on_dev, keep = self._f32_rows(emb)
@@ -904,10 +926,22 @@ class Context(object):
         N = int(rs[-1])
         labels = np.zeros(T, np.int32)
         log = np.zeros((max(T - 1, 1), 4), np.float64)
-        n = C.c_int32(0)
-        check(self._l.pvf_cluster_tracks_f32(self._h, p, stride, n_src, on_dev, None if order is None else ptr(order), N, int(decimals), ptr(rs), T,
-                                             int(metric), float(threshold), ptr(labels), ptr(log), C.byref(n)))
-        return labels, log[:n.value]
+        n, nb = C.c_int32(0), C.c_int32(0)
+        if extent is not None:
+            e = self._extent(extent, T)
+            check(self._l.pvf_cluster_tracks_f32_cooccur(self._h, p, stride, n_src, on_dev, None if order is None else ptr(order), N, int(decimals),
+                                                         ptr(rs), T, int(metric), float(threshold), ptr(labels), ptr(log), C.byref(n),
+                                                         ptr(e), C.byref(nb), int(flags)))
+        else:
+            check(self._l.pvf_cluster_tracks_f32(self._h, p, stride, n_src, on_dev, None if order is None else ptr(order), N, int(decimals), ptr(rs), T,
+                                                 int(metric), float(threshold), ptr(labels), ptr(log), C.byref(n)))
+        return labels, log[:n.value], nb.value
+
+    def cluster_tracks_f32(self, emb, order, row_start, threshold, decimals=5, metric=0):
+        return self._cluster_tracks_f32(emb, order, row_start, threshold, decimals, metric)[:2]
+
+    def cluster_tracks_f32_cooccur(self, emb, order, row_start, threshold, decimals=5, metric=0, *, extent, flags=0):
+        return self._cluster_tracks_f32(emb, order, row_start, threshold, decimals, metric, self._extent(extent, len(row_start) - 1), flags)
 
     def pair_upper_rows_f32(self, emb, order, row_start, track0, track1, decimals=5, out=None):
         """the upper-triangle entries of rows [track0, track1) of the track-pair matrix, compact [(track1 - track0), T]: into `out`
@@ -928,7 +962,7 @@ class Context(object):
                                               ptr(rs), T, int(track0), int(track1), op, odev))
         return res
 
-    def cluster_upper(self, U, row_start, threshold):
+    def _cluster_upper(self, U, row_start, threshold, extent=None, flags=0):
         """mirror + agglomeration of an assembled upper triangle: U numpy [T, T] or a DeviceRows of T rows of T float64"""
         rs = np.ascontiguousarray(row_start, np.int32)
         T = len(rs) - 1
@@ -941,9 +975,20 @@ class Context(object):
             p, on_dev = ptr(U), 0
         labels = np.zeros(T, np.int32)
         log = np.zeros((max(T - 1, 1), 4), np.float64)
-        n = C.c_int32(0)
-        check(self._l.pvf_cluster_upper(self._h, p, on_dev, ptr(rs), T, float(threshold), ptr(labels), ptr(log), C.byref(n)))
-        return labels, log[:n.value]
+        n, nb = C.c_int32(0), C.c_int32(0)
+        if extent is not None:
+            e = self._extent(extent, T)
+            check(self._l.pvf_cluster_upper_cooccur(self._h, p, on_dev, ptr(rs), T, float(threshold), ptr(labels), ptr(log), C.byref(n),
+                                                    ptr(e), C.byref(nb), int(flags)))
+        else:
+            check(self._l.pvf_cluster_upper(self._h, p, on_dev, ptr(rs), T, float(threshold), ptr(labels), ptr(log), C.byref(n)))
+        return labels, log[:n.value], nb.value
+
+    def cluster_upper(self, U, row_start, threshold):
+        return self._cluster_upper(U, row_start, threshold)[:2]
+
+    def cluster_upper_cooccur(self, U, row_start, threshold, extent, flags=0):
+        return self._cluster_upper(U, row_start, threshold, self._extent(extent, len(row_start) - 1), flags)
 
     def pair_mean_dist_rows(self, X, row_start, track0, track1):
         """the complete rows [track0, track1) of the T x T track-pair mean-distance matrix (other rows zero): j > i computed, j < i mirrored"""
@@ -961,15 +1006,26 @@ class Context(object):
         check(fn(self._h, ptr(X), X.shape[0], X.shape[1], ptr(rs), T, int(track0), int(track1), ptr(D)))
         return D
 
-    def cluster_dist(self, D, row_start, threshold):
+    def _cluster_dist(self, D, row_start, threshold, extent=None, flags=0):
         D = np.ascontiguousarray(D, np.float64)
         rs = np.ascontiguousarray(row_start, np.int32)
         T = len(rs) - 1
         labels = np.zeros(T, np.int32)
         log = np.zeros((max(T - 1, 1), 4), np.float64)
-        n = C.c_int32(0)
-        check(self._l.pvf_cluster_dist(self._h, ptr(D), ptr(rs), T, float(threshold), ptr(labels), ptr(log), C.byref(n)))
-        return labels, log[:n.value]
+        n, nb = C.c_int32(0), C.c_int32(0)
+        if extent is not None:
+            e = self._extent(extent, T)
+            check(self._l.pvf_cluster_dist_cooccur(self._h, ptr(D), ptr(rs), T, float(threshold), ptr(labels), ptr(log), C.byref(n),
+                                                   ptr(e), C.byref(nb), int(flags)))
+        else:
+            check(self._l.pvf_cluster_dist(self._h, ptr(D), ptr(rs), T, float(threshold), ptr(labels), ptr(log), C.byref(n)))
+        return labels, log[:n.value], nb.value
+
+    def cluster_dist(self, D, row_start, threshold):
+        return self._cluster_dist(D, row_start, threshold)[:2]
+
+    def cluster_dist_cooccur(self, D, row_start, threshold, extent, flags=0):
+        return self._cluster_dist(D, row_start, threshold, self._extent(extent, len(row_start) - 1), flags)
 
     # ---- measurement
     def detector_screening(self, on=True, list_cap=0):

@@ -4,12 +4,16 @@ that within-identity distances sit at 0.3-0.5 and between-identity ones near 0.8
 clustering.py:138), T = 10 000 tracks with 1 (N = 1e4) or 10 (N = 1e5) rows each.  Times K10 (pair_tiles_k on the f64 matrix cores)
 and K11 (hac_persist_k) with the library's HIP events and checks the result against the generator's ground truth.
     python tools/c5_cluster.py [out.json]
+The 10 000 x 10 case is run a second time with the do-not-cooccur constraint (clustering.py:142-143; FaceClustering(constraint='cooccur')):
+extents drawn so that about one pair in a hundred is forbidden; the agglomeration's time with it (the stamping kernel included and also
+on its own, beside a plain fill of the same T x T matrix) stands next to the time without.
 """
 import json
 import os
 import sys
 import time
 import numpy as np
+import torch  # noqa: F401  first, as in bench.py: the process then runs on the HIP runtime torch ships (used for the plain fill below)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -26,6 +30,45 @@ def make(T, rows, K=500, seed=20260925):
     x = cent[np.repeat(ident, rows)] + 0.05 * rng.normal(size=(T * rows, 128))
     x = np.round(0.55 * x / np.linalg.norm(x, axis=1, keepdims=True), 5)
     return x, (np.arange(T + 1) * rows).astype(np.int32), ident
+
+
+def extents(T, span=300.0, seed=20261018):
+    """(start, end) per track: 0.5-2.5 s long, starts uniform over `span` seconds -- two tracks intersect with probability ~ 2 * 1.5 / span"""
+    rng = np.random.default_rng(seed)
+    start = np.round(rng.uniform(0.0, span, T), 3)
+    return np.stack([start, start + np.round(rng.uniform(0.5, 2.5, T), 3)], axis=1)
+
+
+def constrained(ctx, X, rs, free_labels, reps=3):
+    """the same agglomeration with the constraint: HIP-event times of the `hac` family (stamping included) and of the stamping kernel
+    alone (one launch between two HIP events per call), the latter beside torch's fill of a matrix of the same size timed the same way"""
+    T = len(rs) - 1
+    ext = extents(T)
+    hac, stamp = [], []
+    for _ in range(reps):
+        ctx.prof_reset(); ctx.prof_enable(True)
+        labels, log, n_blocked = ctx.cluster_tracks_cooccur(X, rs, 0.6, extent=ext)
+        ctx.prof_enable(False)
+        hac.append(ctx.prof_get("hac")[0]); stamp.append(ctx.prof_get("cooccur_stamp")[0])
+    s, e = ext[:, 0], ext[:, 1]
+    viol = viol_free = 0
+    for i0 in range(0, T, 1000):                          # co-occurring pairs that share a label, with and without the constraint
+        co = (np.minimum(e[i0:i0 + 1000, None], e[None, :]) - np.maximum(s[i0:i0 + 1000, None], s[None, :])) > 1e-6
+        co &= np.arange(i0, min(i0 + 1000, T))[:, None] < np.arange(T)[None, :]
+        viol += int((co & (labels[i0:i0 + 1000, None] == labels[None, :])).sum())
+        viol_free += int((co & (free_labels[i0:i0 + 1000, None] == free_labels[None, :])).sum())
+    # the plain fill, timed the way the stamp is: one launch between two events per repetition, after two warm-up fills
+    m = torch.empty(T * T, dtype=torch.float64, device="cuda")
+    fill = []
+    for rep in range(2 + reps):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        ev[0].record(); m.fill_(float("inf")); ev[1].record(); torch.cuda.synchronize()
+        if rep >= 2:
+            fill.append(ev[0].elapsed_time(ev[1]))
+    return {"forbidden_pairs": int(n_blocked), "forbidden_fraction": round(n_blocked / (T * (T - 1) / 2.0), 5), "hac_ms_constrained": [round(v, 3) for v in hac],
+            "stamp_ms": [round(v, 4) for v in stamp], "plain_fill_ms_same_matrix": [round(v, 4) for v in fill],
+            "merges": int(len(log)), "clusters": int(len(set(labels.tolist()))), "nan_in_log": bool(np.isnan(log).any()),
+            "cooccurring_pairs_sharing_a_label": viol, "cooccurring_pairs_sharing_a_label_without_constraint": viol_free}
 
 
 def main():  # noqa: C901
@@ -70,6 +113,8 @@ def main():  # noqa: C901
                     "merges": int(len(log)), "merges_per_s": round(len(log) / max(hac_ms * 1e-3, 1e-9)),
                     "hac_D_bytes": int(T) * int(T) * 8, "clusters": int(len(set(labels.tolist()))), "identities": int(len(set(ident.tolist()))),
                     "clusters_pure": bool(pure), "one_cluster_per_identity": bool(one)})
+        if (T, rows) == (10000, 10):
+            res[-1]["do_not_cooccur"] = constrained(ctx, X, rs, labels)
         print(json.dumps(res[-1]))
         sys.stdout.flush()
     if out:
