@@ -878,141 +878,113 @@ extern "C" int32_t pvf_pair_upper_rows_f32(pvf_handle h, const float* emb, int64
     API_END
 }
 
-extern "C" int32_t pvf_cluster_dist(pvf_handle h, const double* D, const int32_t* row_start, int32_t T, double threshold, int32_t* labels,
-                                    double* merge_log, int32_t* n_merges)
+// ---- clustering.  Each entry has a _cooccur twin with the do-not-cooccur constraint the reference names and leaves switched off
+// (face/clustering.py:142-143: `# constraint = DoNotCooccur()` / `constraint = None`): extent = the T x 2 (start, end) seconds of the
+// tracks; pairs whose extents intersect are never merged (cooccur_stamp_k + the constrained agglomeration, cluster.hip).  flags bit 0: a
+// test switch, see pvface.h.  A pair shares one body; the entry without a constraint passes no Cooccur.
+struct Cooccur { const double* extent; int32_t* n_blocked; int32_t flags; };
+// (checked in the entry, before the table is uploaded and the pair distances are computed: a bad extent costs nothing on the device)
+static void check_cooccur(const std::string& name, const Cooccur* co, int32_t T)
+{
+    if (!co) return;
+    PVF_REQUIRE(co->extent && co->n_blocked, name + ": extent and n_blocked are required (the entry without a constraint takes none)");
+    PVF_REQUIRE((co->flags & ~1) == 0, name + ": unknown flags");
+    PVF_REQUIRE(T > 0, name + ": bad arguments");
+    for (int32_t i = 0; i < T; ++i) {
+        PVF_REQUIRE(std::isfinite(co->extent[2 * i]) && std::isfinite(co->extent[2 * i + 1]), "cluster: a track extent is not finite");
+        PVF_REQUIRE(co->extent[2 * i + 1] >= co->extent[2 * i], "cluster: a track extent ends before it starts");
+    }
+}
+static void run_hac(Ctx* c, double* dD, const int32_t* row_start, int32_t T, double threshold, int32_t* labels, double* merge_log, int32_t* n_merges,
+                    const Cooccur* co)
+{
+    const int n = co ? hac_dev(c, dD, row_start, T, threshold, labels, merge_log, co->extent, co->n_blocked, co->flags)
+                     : hac_dev(c, dD, row_start, T, threshold, labels, merge_log);
+    if (n_merges) *n_merges = n;
+}
+
+// src: the full matrix (mirror false, host memory) or its upper triangle (mirror true)
+static int32_t cluster_matrix(const std::string& name, pvf_handle h, const double* src, bool on_device, bool mirror, const int32_t* row_start, int32_t T,
+                              double threshold, int32_t* labels, double* merge_log, int32_t* n_merges, const Cooccur* co)
 {
     API_BEGIN
     ENTER(c, h);
-    PVF_REQUIRE(T > 0 && D && row_start && labels, "pvf_cluster_dist: bad arguments");
-    c->s_clu1.ensure((size_t)T * T * sizeof(double) + (size_t)T * 64 + 4096);
+    PVF_REQUIRE(T > 0 && src && row_start && labels, name + ": bad arguments");
+    check_cooccur(name, co, T);
+    c->s_clu1.ensure(dist_matrix_bytes(T));
     double* dD = c->s_clu1.as<double>();
-    HIP_CHECK(hipMemcpyAsync(dD, D, (size_t)T * T * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    const int n = hac_dev(c, dD, row_start, T, threshold, labels, merge_log);
-    if (n_merges) *n_merges = n;
+    HIP_CHECK(hipMemcpyAsync(dD, src, (size_t)T * T * sizeof(double), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+    if (mirror) mirror_upper_dev(c, dD, T);
+    run_hac(c, dD, row_start, T, threshold, labels, merge_log, n_merges, co);
     API_END
+}
+
+static int32_t cluster_table(const std::string& name, pvf_handle h, const PairInput& in, int32_t N, int32_t dim, const int32_t* row_start, int32_t T,
+                             int32_t metric, double threshold, int32_t* labels, double* merge_log, int32_t* n_merges, const Cooccur* co)
+{
+    API_BEGIN
+    ENTER(c, h);
+    PVF_REQUIRE((in.X || in.emb) && row_start && labels, name + ": bad arguments");
+    check_cooccur(name, co, T);
+    double* dD = nullptr;
+    pair_mean_dist_dev(c, in, N, dim, row_start, T, PairOutput(), &dD, 0, T, metric, true);
+    run_hac(c, dD, row_start, T, threshold, labels, merge_log, n_merges, co);
+    API_END
+}
+
+extern "C" int32_t pvf_cluster_dist(pvf_handle h, const double* D, const int32_t* row_start, int32_t T, double threshold, int32_t* labels,
+                                    double* merge_log, int32_t* n_merges)
+{
+    return cluster_matrix("pvf_cluster_dist", h, D, false, false, row_start, T, threshold, labels, merge_log, n_merges, nullptr);
+}
+extern "C" int32_t pvf_cluster_dist_cooccur(pvf_handle h, const double* D, const int32_t* row_start, int32_t T, double threshold, int32_t* labels,
+                                            double* merge_log, int32_t* n_merges, const double* extent, int32_t* n_blocked, int32_t flags)
+{
+    const Cooccur co{extent, n_blocked, flags};
+    return cluster_matrix("pvf_cluster_dist_cooccur", h, D, false, false, row_start, T, threshold, labels, merge_log, n_merges, &co);
 }
 
 extern "C" int32_t pvf_cluster_upper(pvf_handle h, const double* U, int32_t on_device, const int32_t* row_start, int32_t T, double threshold,
                                      int32_t* labels, double* merge_log, int32_t* n_merges)
 {
-    API_BEGIN
-    ENTER(c, h);
-    PVF_REQUIRE(T > 0 && U && row_start && labels, "pvf_cluster_upper: bad arguments");
-    c->s_clu1.ensure((size_t)T * T * sizeof(double) + (size_t)T * 64 + 4096);
-    double* dD = c->s_clu1.as<double>();
-    HIP_CHECK(hipMemcpyAsync(dD, U, (size_t)T * T * sizeof(double), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
-    mirror_upper_dev(c, dD, T);
-    const int n = hac_dev(c, dD, row_start, T, threshold, labels, merge_log);
-    if (n_merges) *n_merges = n;
-    API_END
+    return cluster_matrix("pvf_cluster_upper", h, U, on_device != 0, true, row_start, T, threshold, labels, merge_log, n_merges, nullptr);
+}
+extern "C" int32_t pvf_cluster_upper_cooccur(pvf_handle h, const double* U, int32_t on_device, const int32_t* row_start, int32_t T, double threshold,
+                                             int32_t* labels, double* merge_log, int32_t* n_merges, const double* extent, int32_t* n_blocked, int32_t flags)
+{
+    const Cooccur co{extent, n_blocked, flags};
+    return cluster_matrix("pvf_cluster_upper_cooccur", h, U, on_device != 0, true, row_start, T, threshold, labels, merge_log, n_merges, &co);
 }
 
 extern "C" int32_t pvf_cluster_tracks(pvf_handle h, const double* X, int32_t N, int32_t dim, const int32_t* row_start, int32_t T,
                                       double threshold, int32_t* labels, double* merge_log, int32_t* n_merges)
 {
-    API_BEGIN
-    ENTER(c, h);
-    PVF_REQUIRE(X && row_start && labels, "pvf_cluster_tracks: bad arguments");
-    double* dD = nullptr;
-    pair_mean_dist_dev(c, table_f64(X), N, dim, row_start, T, PairOutput(), &dD, 0, T, 0, true);
-    const int n = hac_dev(c, dD, row_start, T, threshold, labels, merge_log);
-    if (n_merges) *n_merges = n;
-    API_END
+    return cluster_table("pvf_cluster_tracks", h, table_f64(X), N, dim, row_start, T, 0, threshold, labels, merge_log, n_merges, nullptr);
+}
+extern "C" int32_t pvf_cluster_tracks_cooccur(pvf_handle h, const double* X, int32_t N, int32_t dim, const int32_t* row_start, int32_t T,
+                                              double threshold, int32_t* labels, double* merge_log, int32_t* n_merges, const double* extent,
+                                              int32_t* n_blocked, int32_t flags)
+{
+    const Cooccur co{extent, n_blocked, flags};
+    return cluster_table("pvf_cluster_tracks_cooccur", h, table_f64(X), N, dim, row_start, T, 0, threshold, labels, merge_log, n_merges, &co);
 }
 
 extern "C" int32_t pvf_cluster_tracks_f32(pvf_handle h, const float* emb, int64_t row_stride_bytes, int32_t n_src, int32_t emb_on_device,
                                           const int32_t* order, int32_t N, int32_t decimals, const int32_t* row_start, int32_t T, int32_t metric,
                                           double threshold, int32_t* labels, double* merge_log, int32_t* n_merges)
 {
-    API_BEGIN
-    ENTER(c, h);
-    PVF_REQUIRE(emb && row_start && labels, "pvf_cluster_tracks_f32: bad arguments");
-    double* dD = nullptr;
-    pair_mean_dist_dev(c, table_f32(emb, row_stride_bytes, n_src, emb_on_device, order, decimals), N, 128, row_start, T, PairOutput(), &dD, 0, T, metric, true);
-    const int n = hac_dev(c, dD, row_start, T, threshold, labels, merge_log);
-    if (n_merges) *n_merges = n;
-    API_END
+    return cluster_table("pvf_cluster_tracks_f32", h, table_f32(emb, row_stride_bytes, n_src, emb_on_device, order, decimals), N, 128, row_start, T, metric,
+                         threshold, labels, merge_log, n_merges, nullptr);
 }
-
-// ---- the same four with the do-not-cooccur constraint the reference names and leaves switched off (face/clustering.py:142-143:
-// `# constraint = DoNotCooccur()` / `constraint = None`): extent = the T x 2 (start, end) seconds of the tracks; pairs whose extents
-// intersect are never merged (cooccur_stamp_k + the constrained agglomeration, cluster.hip).  flags bit 0: a test switch, see pvface.h.
-// (checked in the entry, before the table is uploaded and the pair distances are computed: a bad extent costs nothing on the device)
-static void check_extents(const double* extent, int32_t T)
-{
-    for (int32_t i = 0; i < T; ++i) {
-        PVF_REQUIRE(std::isfinite(extent[2 * i]) && std::isfinite(extent[2 * i + 1]), "cluster: a track extent is not finite");
-        PVF_REQUIRE(extent[2 * i + 1] >= extent[2 * i], "cluster: a track extent ends before it starts");
-    }
-}
-#define COOCCUR_ARGS(name)                                                                                                         \
-    PVF_REQUIRE(extent && n_blocked, name ": extent and n_blocked are required (the entry without a constraint takes none)");   \
-    PVF_REQUIRE((flags & ~1) == 0, name ": unknown flags");                                                                     \
-    PVF_REQUIRE(T > 0, name ": bad arguments");                                                                                 \
-    check_extents(extent, T)
-
-extern "C" int32_t pvf_cluster_dist_cooccur(pvf_handle h, const double* D, const int32_t* row_start, int32_t T, double threshold, int32_t* labels,
-                                            double* merge_log, int32_t* n_merges, const double* extent, int32_t* n_blocked, int32_t flags)
-{
-    API_BEGIN
-    ENTER(c, h);
-    PVF_REQUIRE(T > 0 && D && row_start && labels, "pvf_cluster_dist_cooccur: bad arguments");
-    COOCCUR_ARGS("pvf_cluster_dist_cooccur");
-    c->s_clu1.ensure((size_t)T * T * sizeof(double) + (size_t)T * 64 + 4096);
-    double* dD = c->s_clu1.as<double>();
-    HIP_CHECK(hipMemcpyAsync(dD, D, (size_t)T * T * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    const int n = hac_dev(c, dD, row_start, T, threshold, labels, merge_log, extent, n_blocked, flags);
-    if (n_merges) *n_merges = n;
-    API_END
-}
-
-extern "C" int32_t pvf_cluster_upper_cooccur(pvf_handle h, const double* U, int32_t on_device, const int32_t* row_start, int32_t T, double threshold,
-                                             int32_t* labels, double* merge_log, int32_t* n_merges, const double* extent, int32_t* n_blocked, int32_t flags)
-{
-    API_BEGIN
-    ENTER(c, h);
-    PVF_REQUIRE(T > 0 && U && row_start && labels, "pvf_cluster_upper_cooccur: bad arguments");
-    COOCCUR_ARGS("pvf_cluster_upper_cooccur");
-    c->s_clu1.ensure((size_t)T * T * sizeof(double) + (size_t)T * 64 + 4096);
-    double* dD = c->s_clu1.as<double>();
-    HIP_CHECK(hipMemcpyAsync(dD, U, (size_t)T * T * sizeof(double), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
-    mirror_upper_dev(c, dD, T);
-    const int n = hac_dev(c, dD, row_start, T, threshold, labels, merge_log, extent, n_blocked, flags);
-    if (n_merges) *n_merges = n;
-    API_END
-}
-
-extern "C" int32_t pvf_cluster_tracks_cooccur(pvf_handle h, const double* X, int32_t N, int32_t dim, const int32_t* row_start, int32_t T,
-                                              double threshold, int32_t* labels, double* merge_log, int32_t* n_merges, const double* extent,
-                                              int32_t* n_blocked, int32_t flags)
-{
-    API_BEGIN
-    ENTER(c, h);
-    PVF_REQUIRE(X && row_start && labels, "pvf_cluster_tracks_cooccur: bad arguments");
-    COOCCUR_ARGS("pvf_cluster_tracks_cooccur");
-    double* dD = nullptr;
-    pair_mean_dist_dev(c, table_f64(X), N, dim, row_start, T, PairOutput(), &dD, 0, T, 0, true);
-    const int n = hac_dev(c, dD, row_start, T, threshold, labels, merge_log, extent, n_blocked, flags);
-    if (n_merges) *n_merges = n;
-    API_END
-}
-
 extern "C" int32_t pvf_cluster_tracks_f32_cooccur(pvf_handle h, const float* emb, int64_t row_stride_bytes, int32_t n_src, int32_t emb_on_device,
                                                   const int32_t* order, int32_t N, int32_t decimals, const int32_t* row_start, int32_t T, int32_t metric,
                                                   double threshold, int32_t* labels, double* merge_log, int32_t* n_merges, const double* extent,
                                                   int32_t* n_blocked, int32_t flags)
 {
-    API_BEGIN
-    ENTER(c, h);
-    PVF_REQUIRE(emb && row_start && labels, "pvf_cluster_tracks_f32_cooccur: bad arguments");
-    COOCCUR_ARGS("pvf_cluster_tracks_f32_cooccur");
-    double* dD = nullptr;
-    pair_mean_dist_dev(c, table_f32(emb, row_stride_bytes, n_src, emb_on_device, order, decimals), N, 128, row_start, T, PairOutput(), &dD, 0, T, metric, true);
-    const int n = hac_dev(c, dD, row_start, T, threshold, labels, merge_log, extent, n_blocked, flags);
-    if (n_merges) *n_merges = n;
-    API_END
+    const Cooccur co{extent, n_blocked, flags};
+    return cluster_table("pvf_cluster_tracks_f32_cooccur", h, table_f32(emb, row_stride_bytes, n_src, emb_on_device, order, decimals), N, 128, row_start, T,
+                         metric, threshold, labels, merge_log, n_merges, &co);
 }
-
 
 // ---- text rows of landmarks.txt / embedding.txt (host) ---------------------------------------------------------------------------------
 // ref: scripts/pyannote-face.py:299-311  "{t:.3f} {identifier:d}" followed by " {v:.5f}" per value, one line per face.  Python's format

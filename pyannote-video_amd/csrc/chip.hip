@@ -236,22 +236,22 @@ void chip_extract_batch(Ctx* c, const std::vector<ChipJob>& jobs, uint8_t* d_out
         }
     }
     // upload descriptors: [levels][n] pyr jobs then [n] xf jobs
-    const size_t pyr_bytes = (size_t)max_levels * n * sizeof(DevPyrJob);
-    const size_t total = pyr_bytes + n * sizeof(DevXfJob) + 64;
-    c->s_chip.ensure(total);
-    uint8_t* hb = reinterpret_cast<uint8_t*>(c->stage.take(total));
-    for (int l = 0; l < max_levels; ++l) memcpy(hb + (size_t)l * n * sizeof(DevPyrJob), pj[l].data(), n * sizeof(DevPyrJob));
-    const size_t xf_off = (pyr_bytes + 15) / 16 * 16;
-    memcpy(hb + xf_off, xf.data(), n * sizeof(DevXfJob));
-    HIP_CHECK(hipMemcpyAsync(c->s_chip.p, hb, xf_off + n * sizeof(DevXfJob), hipMemcpyHostToDevice, c->stream));
+    ScratchLayout lay;
+    const auto sPyr = lay.take<DevPyrJob>((size_t)max_levels * n, 16); const auto sXf = lay.take<DevXfJob>(n, 16);
+    const size_t used = lay.bytes();
+    lay.pad(64);                                              // reason unknown, kept
+    c->s_chip.ensure(lay.bytes());
+    uint8_t* hb = reinterpret_cast<uint8_t*>(c->stage.take(lay.bytes()));      // the same layout in the staging buffer
+    for (int l = 0; l < max_levels; ++l) memcpy(hb + sPyr.off + (size_t)l * n * sizeof(DevPyrJob), pj[l].data(), n * sizeof(DevPyrJob));
+    memcpy(hb + sXf.off, xf.data(), sXf.bytes());
+    HIP_CHECK(hipMemcpyAsync(c->s_chip.p, hb, used, hipMemcpyHostToDevice, c->stream));
     c->stage.sent(c->stream);
     ProfScope ps(c, "chip");
     for (int l = 0; l < max_levels; ++l) {
         if (max_h[l] <= 0 || max_w[l] <= 0) continue;
         hipLaunchKernelGGL(pyr_down2_k, dim3((max_w[l] + PD_TW - 1) / PD_TW, (max_h[l] + PD_TH - 1) / PD_TH, n), dim3(256), 0, c->stream,
-                           reinterpret_cast<const DevPyrJob*>(c->s_chip.as<uint8_t>() + (size_t)l * n * sizeof(DevPyrJob)));
+                           sPyr.in(c->s_chip) + (size_t)l * n);
     }
-    hipLaunchKernelGGL(transform_k, dim3((cols + 63) / 64, rows, n), dim3(64), 0, c->stream,
-                       reinterpret_cast<const DevXfJob*>(c->s_chip.as<uint8_t>() + xf_off), d_out, rows, cols);
+    hipLaunchKernelGGL(transform_k, dim3((cols + 63) / 64, rows, n), dim3(64), 0, c->stream, sXf.in(c->s_chip), d_out, rows, cols);
     // (no synchronisation: the descriptors went through a staging buffer of their own, the device scratch is reused in stream order)
 }

@@ -436,23 +436,24 @@ static void pair_mean_dist_mfma(Ctx* c, const PairInput& in, int N, const int32_
     const int n_ranges = (int)range_b0.size() - 1;
     for (int k = 0; k < n_ranges; ++k) PVF_REQUIRE(range_b0[k + 1] - range_b0[k] <= (1 << 17), "pair_mean_dist: a track of more than a million rows");
     // ---- device buffers
-    auto al = [](size_t v) { return (v + 255) / 256 * 256; };
-    const size_t xb = al((size_t)N * DIM * 8), nbz = al((size_t)N * 8), ib = al((size_t)N * 4), bb = al((size_t)nb * 4), pb = al((size_t)std::max(n_chunks, 1) * T * 8);
-    const size_t rsb = al((size_t)(T + 1) * 4), rgb = al((size_t)(n_ranges + 1) * 4), bigb = al((size_t)std::max<size_t>(big_track.size(), 1) * 4);
-    const size_t tmpb = al(stage_tmp_bytes(in, DIM)), ordb = al(in.order ? (size_t)N * 4 : 0);
-    c->s_clu0.ensure(xb + nbz + 2 * ib + bb + 2 * al((size_t)nb * 16 * 4) + pb + 2 * rsb + rgb + 3 * bigb + tmpb + ordb + 4096);
-    c->s_clu1.ensure((size_t)T * T * sizeof(double) + (size_t)T * 64 + 4096);
-    uint8_t* p = c->s_clu0.as<uint8_t>();
-    auto take = [&](size_t bytes) { uint8_t* q = p; p += bytes; return q; };
-    double* dX = (double*)take(xb); double* dN = (double*)take(nbz);
-    int* dRT = (int*)take(ib); int* dRS = (int*)take(ib);
-    int* dBC = (int*)take(bb);
-    int* dST = (int*)take(al((size_t)nb * 16 * 4)); int* dSP = (int*)take(al((size_t)nb * 16 * 4));
-    double* dP = (double*)take(pb);
-    int* dRow = (int*)take(rsb); int* dRange = (int*)take(rgb);
-    int* dBigT = (int*)take(bigb); int* dBigC0 = (int*)take(bigb); int* dBigNc = (int*)take(bigb);
-    int* dIsBig = (int*)take(rsb);
-    uint8_t* dTmp = take(tmpb); int32_t* dOrder = (int32_t*)take(ordb);
+    ScratchLayout lay;
+    const size_t n_big = std::max<size_t>(big_track.size(), 1);
+    const auto sX = lay.take<double>((size_t)N * DIM), sN = lay.take<double>(N);
+    const auto sRT = lay.take<int>(N), sRS = lay.take<int>(N), sBC = lay.take<int>(nb), sST = lay.take<int>((size_t)nb * 16), sSP = lay.take<int>((size_t)nb * 16);
+    const auto sP = lay.take<double>((size_t)std::max(n_chunks, 1) * T);
+    const auto sRow = lay.take<int>(T + 1), sRange = lay.take<int>(n_ranges + 1);
+    const auto sBigT = lay.take<int>(n_big), sBigC0 = lay.take<int>(n_big), sBigNc = lay.take<int>(n_big), sIsBig = lay.take<int>(T + 1);
+    const auto sTmp = lay.take<uint8_t>(stage_tmp_bytes(in, DIM));
+    const auto sOrder = lay.take<int32_t>(in.order ? (size_t)N : 0);
+    lay.pad(4096);                                          // reason unknown, kept
+    c->s_clu0.ensure(lay.bytes());
+    c->s_clu1.ensure(dist_matrix_bytes(T));
+    double* dX = sX.in(c->s_clu0); double* dN = sN.in(c->s_clu0);
+    int* dRT = sRT.in(c->s_clu0); int* dRS = sRS.in(c->s_clu0); int* dBC = sBC.in(c->s_clu0); int* dST = sST.in(c->s_clu0); int* dSP = sSP.in(c->s_clu0);
+    double* dP = sP.in(c->s_clu0);
+    int* dRow = sRow.in(c->s_clu0); int* dRange = sRange.in(c->s_clu0);
+    int* dBigT = sBigT.in(c->s_clu0); int* dBigC0 = sBigC0.in(c->s_clu0); int* dBigNc = sBigNc.in(c->s_clu0); int* dIsBig = sIsBig.in(c->s_clu0);
+    uint8_t* dTmp = sTmp.in(c->s_clu0); int32_t* dOrder = sOrder.in(c->s_clu0);
     double* dD = c->s_clu1.as<double>();
     auto up = [&](void* d, const void* h, size_t bytes) { if (bytes) HIP_CHECK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, c->stream)); };
     stage_table(c, in, N, DIM, dX, dTmp, dOrder);
@@ -509,19 +510,17 @@ void pair_mean_dist_dev(Ctx* c, const PairInput& in, int N, int dim, const int32
     }
     if (dim == 128) { pair_mean_dist_mfma(c, in, N, row_start, T, out, d_D_keep, t0, t1, metric, mirror); return; }
     PVF_REQUIRE(metric == 0, "pair_mean_dist: cosine is implemented for 128-D rows");
-    auto al = [](size_t v) { return (v + 255) / 256 * 256; };
-    const size_t xb = al((size_t)N * dim * sizeof(double));
-    const size_t sb = al((size_t)N * T * sizeof(double)), db = (size_t)T * T * sizeof(double), rb = al((size_t)(T + 1) * sizeof(int32_t));
-    const size_t tmpb = al(stage_tmp_bytes(in, dim)), ordb = al(in.order ? (size_t)N * 4 : 0);
-    c->s_clu0.ensure(2 * xb + sb + rb + tmpb + ordb + 512);
-    c->s_clu1.ensure(db + (size_t)T * 64 + 4096);
-    uint8_t* p = c->s_clu0.as<uint8_t>();
-    double* dX = reinterpret_cast<double*>(p); p += xb;
-    double* dXt = reinterpret_cast<double*>(p); p += xb;
-    double* dS = reinterpret_cast<double*>(p); p += sb;
-    int32_t* dR = reinterpret_cast<int32_t*>(p); p += rb;
-    uint8_t* dTmp = p; p += tmpb;
-    int32_t* dOrder = reinterpret_cast<int32_t*>(p);
+    ScratchLayout lay;
+    const auto sX = lay.take<double>((size_t)N * dim), sXt = lay.take<double>((size_t)N * dim), sS = lay.take<double>((size_t)N * T);
+    const auto sR = lay.take<int32_t>(T + 1);
+    const auto sTmp = lay.take<uint8_t>(stage_tmp_bytes(in, dim));
+    const auto sOrder = lay.take<int32_t>(in.order ? (size_t)N : 0);
+    lay.pad(512);                                           // reason unknown, kept
+    c->s_clu0.ensure(lay.bytes());
+    c->s_clu1.ensure(dist_matrix_bytes(T));
+    double* dX = sX.in(c->s_clu0); double* dXt = sXt.in(c->s_clu0); double* dS = sS.in(c->s_clu0);
+    int32_t* dR = sR.in(c->s_clu0);
+    uint8_t* dTmp = sTmp.in(c->s_clu0); int32_t* dOrder = sOrder.in(c->s_clu0);
     double* dD = c->s_clu1.as<double>();
     stage_table(c, in, N, dim, dX, dTmp, dOrder);
     HIP_CHECK(hipMemcpyAsync(dR, row_start, (size_t)(T + 1) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
@@ -879,6 +878,28 @@ __global__ void __launch_bounds__(256) cooccur_stamp_k(double* __restrict__ D, i
     if (tid == 0 && cnt[0] + cnt[1] + cnt[2] + cnt[3] > 0) atomicAdd(n_blocked, cnt[0] + cnt[1] + cnt[2] + cnt[3]);
 }
 
+// hac_persist_k<U, CO> for T tracks: U = the entries of a row a thread owns (1024 U >= T).  The launch raises the instantiation's dynamic
+// LDS limit on its first use on a device (a function attribute belongs to the device it was set on).
+template <int U, bool CO>
+static void hac_persist_launch(Ctx* c, const HacState& h)
+{
+    static std::atomic<uint64_t> attr_on{0};
+    const uint64_t dev_bit = 1ull << (c->device & 63);
+    if (!(attr_on.load() & dev_bit)) {
+        HIP_CHECK(hipFuncSetAttribute((const void*)hac_persist_k<U, CO>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)hac_persist_lds(std::min(1024 * U, HAC_PERSIST_MAX_T))));
+        attr_on.fetch_or(dev_bit);
+    }
+    hipLaunchKernelGGL((hac_persist_k<U, CO>), dim3(1), dim3(1024), hac_persist_lds(h.T), c->stream, h);   // rmin f64, rarg i32, re-scan list u16, alive bits
+}
+template <bool CO>
+static void hac_persist(Ctx* c, const HacState& h)
+{
+    if (h.T <= 1024) hac_persist_launch<1, CO>(c, h);
+    else if (h.T <= 3072) hac_persist_launch<3, CO>(c, h);
+    else hac_persist_launch<10, CO>(c, h);
+}
+
 // extent: optional T x 2 float64 (start, end) per track, checked by the caller (api.hip refuses bad ones before any device work)
 // -> the constrained agglomeration (n_blocked: forbidden pairs i < j);
 // flags bit 0: the launch-per-merge path whatever T (a test switch: that path is otherwise reached above HAC_PERSIST_MAX_T only)
@@ -888,29 +909,23 @@ int hac_dev(Ctx* c, double* d_D, const int32_t* row_start, int T, double thresho
     for (int i = 0; i < T; ++i) labels[i] = i;
     if (n_blocked) *n_blocked = 0;
     if (T < 2) return 0;
-    const size_t need = (size_t)T * (8 + 4 + 4 + 4 + 8) + 4 * 8 + (size_t)T * 4 * 8 + 64 + (size_t)(T + 1) * 4 + 512 + (extent ? (size_t)T * 16 + 64 : 0);
-    c->s_misc.ensure(need);
-    uint8_t* p = c->s_misc.as<uint8_t>();
-    auto take = [&](size_t bytes) { uint8_t* q = p; p += (bytes + 63) / 64 * 64; return q; };
-    // note: the bump sizes above leave slack for the 64-byte rounding
-    c->s_misc.ensure(need + 64 * (extent ? 12 : 10));
-    p = c->s_misc.as<uint8_t>();
+    ScratchLayout lay;
+    const auto sRmin = lay.take<double>(T, 64), sSize = lay.take<double>(T, 64), sBest = lay.take<double>(4, 64), sLog = lay.take<double>((size_t)T * 4, 64);
+    const auto sRarg = lay.take<int>(T, 64), sAlive = lay.take<int>(T, 64), sDirty = lay.take<int>(T, 64), sMerges = lay.take<int>(16, 64);
+    const auto sR = lay.take<int32_t>(T + 1, 64);
+    const auto sExt = lay.take<double>(extent ? (size_t)T * 2 : 0, 64);
+    const auto sBlocked = lay.take<int>(extent ? 16 : 0, 64);
+    lay.pad(1280);                                          // reason unknown, kept (slack terms of 512 and of 64 per array)
+    c->s_misc.ensure(lay.bytes());
     HacState h;
     h.D = d_D; h.T = T; h.threshold = threshold;
-    h.rmin = (double*)take((size_t)T * 8);
-    h.size = (double*)take((size_t)T * 8);
-    h.best = (double*)take(4 * 8);
-    h.log = (double*)take((size_t)T * 4 * 8);
-    h.rarg = (int*)take((size_t)T * 4);
-    h.alive = (int*)take((size_t)T * 4);
-    h.dirty = (int*)take((size_t)T * 4);
-    h.n_merges = (int*)take(64);
-    int32_t* dR = (int32_t*)take((size_t)(T + 1) * 4);
+    h.rmin = sRmin.in(c->s_misc); h.size = sSize.in(c->s_misc); h.best = sBest.in(c->s_misc); h.log = sLog.in(c->s_misc);
+    h.rarg = sRarg.in(c->s_misc); h.alive = sAlive.in(c->s_misc); h.dirty = sDirty.in(c->s_misc); h.n_merges = sMerges.in(c->s_misc);
+    int32_t* dR = sR.in(c->s_misc);
     HIP_CHECK(hipMemcpyAsync(dR, row_start, (size_t)(T + 1) * 4, hipMemcpyHostToDevice, c->stream));
     double* dExt = nullptr; int* dBlocked = nullptr;
     if (extent) {
-        dExt = (double*)take((size_t)T * 16);
-        dBlocked = (int*)take(64);
+        dExt = sExt.in(c->s_misc); dBlocked = sBlocked.in(c->s_misc);
         HIP_CHECK(hipMemcpyAsync(dExt, extent, (size_t)T * 16, hipMemcpyHostToDevice, c->stream));
         HIP_CHECK(hipMemsetAsync(dBlocked, 0, 4, c->stream));
     }
@@ -923,41 +938,19 @@ int hac_dev(Ctx* c, double* d_D, const int32_t* row_start, int T, double thresho
     hipLaunchKernelGGL(hac_row_min_k, dim3(T), dim3(256), 0, c->stream, h, 0);
     double hbest[4];
     if (T <= HAC_PERSIST_MAX_T && !(flags & 1)) {
-        const size_t lds = hac_persist_lds(T);           // rmin f64, rarg i32, re-scan list u16, alive bits
-        static std::atomic<uint64_t> attr_on{0};          // per device (a function attribute belongs to the device it was set on)
-        const uint64_t dev_bit = 1ull << (c->device & 63);
-        if (!(attr_on.load() & dev_bit)) {
-            HIP_CHECK(hipFuncSetAttribute((const void*)hac_persist_k<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hac_persist_lds(1024)));
-            HIP_CHECK(hipFuncSetAttribute((const void*)hac_persist_k<3, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hac_persist_lds(3072)));
-            HIP_CHECK(hipFuncSetAttribute((const void*)hac_persist_k<10, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hac_persist_lds(HAC_PERSIST_MAX_T)));
-            attr_on.fetch_or(dev_bit);
-        }
-        static std::atomic<uint64_t> attr_co_on{0};       // the constrained instantiations: on their first use
-        if (extent && !(attr_co_on.load() & dev_bit)) {
-            HIP_CHECK(hipFuncSetAttribute((const void*)hac_persist_k<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hac_persist_lds(1024)));
-            HIP_CHECK(hipFuncSetAttribute((const void*)hac_persist_k<3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hac_persist_lds(3072)));
-            HIP_CHECK(hipFuncSetAttribute((const void*)hac_persist_k<10, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hac_persist_lds(HAC_PERSIST_MAX_T)));
-            attr_co_on.fetch_or(dev_bit);
-        }
-        if (extent) {
-            if (T <= 1024) hipLaunchKernelGGL((hac_persist_k<1, true>), dim3(1), dim3(1024), lds, c->stream, h);
-            else if (T <= 3072) hipLaunchKernelGGL((hac_persist_k<3, true>), dim3(1), dim3(1024), lds, c->stream, h);
-            else hipLaunchKernelGGL((hac_persist_k<10, true>), dim3(1), dim3(1024), lds, c->stream, h);
-        }
-        else if (T <= 1024) hipLaunchKernelGGL((hac_persist_k<1, false>), dim3(1), dim3(1024), lds, c->stream, h);
-        else if (T <= 3072) hipLaunchKernelGGL((hac_persist_k<3, false>), dim3(1), dim3(1024), lds, c->stream, h);
-        else hipLaunchKernelGGL((hac_persist_k<10, false>), dim3(1), dim3(1024), lds, c->stream, h);
-    } else
-    for (int it = 0; it < T - 1; ++it) {
-        hipLaunchKernelGGL(hac_argmin_k, dim3(1), dim3(1024), 0, c->stream, h);
-        if (extent) hipLaunchKernelGGL(hac_merge_k<true>, dim3((T + 255) / 256), dim3(256), 0, c->stream, h);
-        else hipLaunchKernelGGL(hac_merge_k<false>, dim3((T + 255) / 256), dim3(256), 0, c->stream, h);
-        hipLaunchKernelGGL(hac_finish_merge_k, dim3(1), dim3(1), 0, c->stream, h);
-        hipLaunchKernelGGL(hac_row_min_k, dim3(T), dim3(256), 0, c->stream, h, 1);
-        if ((it & 63) == 63) {
-            HIP_CHECK(hipMemcpyAsync(hbest, h.best, sizeof hbest, hipMemcpyDeviceToHost, c->stream));
-            HIP_CHECK(hipStreamSynchronize(c->stream));
-            if (hbest[3] != 0.0) break;
+        if (!extent) hac_persist<false>(c, h); else hac_persist<true>(c, h);
+    } else {
+        void (*const merge_k)(HacState) = extent ? hac_merge_k<true> : hac_merge_k<false>;
+        for (int it = 0; it < T - 1; ++it) {
+            hipLaunchKernelGGL(hac_argmin_k, dim3(1), dim3(1024), 0, c->stream, h);
+            hipLaunchKernelGGL(merge_k, dim3((T + 255) / 256), dim3(256), 0, c->stream, h);
+            hipLaunchKernelGGL(hac_finish_merge_k, dim3(1), dim3(1), 0, c->stream, h);
+            hipLaunchKernelGGL(hac_row_min_k, dim3(T), dim3(256), 0, c->stream, h, 1);
+            if ((it & 63) == 63) {
+                HIP_CHECK(hipMemcpyAsync(hbest, h.best, sizeof hbest, hipMemcpyDeviceToHost, c->stream));
+                HIP_CHECK(hipStreamSynchronize(c->stream));
+                if (hbest[3] != 0.0) break;
+            }
         }
     }
     HIP_CHECK(hipGetLastError());

@@ -1284,6 +1284,18 @@ static void screen_verdict(Ctx* c, const int* ctl)
     }
 }
 
+// candidate buffers, device and pinned alike: the per-frame counts with the screening pass's counters behind them, then `per_frame`
+// candidate records per frame
+struct CandLayout { ScratchLayout lay; ScratchSlot<int> counts; ScratchSlot<CandRec> cands; };
+static CandLayout cand_layout(int frames, int per_frame)
+{
+    CandLayout l;
+    l.counts = l.lay.take<int>(frames + SCR_CTL_INTS, 64);
+    l.cands = l.lay.take<CandRec>((size_t)frames * per_frame, 64);
+    l.lay.pad(64);                                            // reason unknown, kept
+    return l;
+}
+
 void det_run_batch(Ctx* c, const std::vector<Frame>& frames, int upsample, double adjust, std::vector<std::vector<RawDet>>& raw_sorted)
 {
     const DetectorModel& m = c->det;
@@ -1291,19 +1303,17 @@ void det_run_batch(Ctx* c, const std::vector<Frame>& frames, int upsample, doubl
     PVF_REQUIRE(!frames.empty(), "no frames");
     const int B = (int)frames.size();
     const int cap = c->det_cand_cap;
-    const size_t cnt_bytes = (((size_t)(B + SCR_CTL_INTS) * sizeof(int) + 63) / 64) * 64;     // per-frame counts + the screening pass's counters
-    c->s_cand.ensure((size_t)B * cap * sizeof(CandRec) + cnt_bytes + 64);
-    int* d_counts = c->s_cand.as<int>();
-    CandRec* d_cands = reinterpret_cast<CandRec*>(c->s_cand.as<uint8_t>() + cnt_bytes);
+    const CandLayout cl = cand_layout(B, cap);
+    c->s_cand.ensure(cl.lay.bytes());
+    int* d_counts = cl.counts.in(c->s_cand); CandRec* d_cands = cl.cands.in(c->s_cand);
     HIP_CHECK(hipMemsetAsync(d_counts, 0, (size_t)(B + SCR_CTL_INTS) * sizeof(int), c->det_stream));
     ScoreParams sp;
     for (int f = 0; f < 8; ++f) sp.thresh[f] = f < m.n_filters ? (float)((double)m.thresh[f] + adjust) : 3.0e38f;
     sp.n_filters = m.n_filters; sp.cap = cap;
     det_run_batch_ml(c, frames, upsample, sp, d_counts, d_cands);
     HIP_CHECK(hipGetLastError());
-    c->h_cand.ensure((size_t)B * cap * sizeof(CandRec) + cnt_bytes + 64);
-    int* h_counts = c->h_cand.as<int>();
-    CandRec* h_cands = reinterpret_cast<CandRec*>(c->h_cand.as<uint8_t>() + cnt_bytes);
+    c->h_cand.ensure(cl.lay.bytes());
+    int* h_counts = cl.counts.in(c->h_cand); CandRec* h_cands = cl.cands.in(c->h_cand);
     HIP_CHECK(hipMemcpyAsync(h_counts, d_counts, (size_t)(B + SCR_CTL_INTS) * sizeof(int), hipMemcpyDeviceToHost, c->det_stream));
     HIP_CHECK(hipStreamSynchronize(c->det_stream));
     screen_verdict(c, h_counts + B);
@@ -1361,34 +1371,30 @@ void det_run_many(Ctx* c, const std::vector<Frame>& frames, int batch, int upsam
     ScoreParams sp;
     for (int f = 0; f < 8; ++f) sp.thresh[f] = f < m.n_filters ? (float)((double)m.thresh[f] + adjust) : 3.0e38f;
     sp.n_filters = m.n_filters; sp.cap = cap;
-    const size_t cnt_bytes = (((size_t)(batch + SCR_CTL_INTS) * sizeof(int) + 63) / 64) * 64;     // per-frame counts + the screening pass's counters
+    const CandLayout dl = cand_layout(batch, cap), hl = cand_layout(batch, PF);        // device: every candidate; pinned: the prefetched ones
     for (int k = 0; k < 2; ++k) {
-        c->s_cand2[k].ensure(cnt_bytes + (size_t)batch * cap * sizeof(CandRec));
-        c->h_cand2[k].ensure(cnt_bytes + (size_t)batch * PF * sizeof(CandRec));
+        c->s_cand2[k].ensure(dl.lay.bytes());
+        c->h_cand2[k].ensure(hl.lay.bytes());
         if (!c->det_ev[k]) HIP_CHECK(hipEventCreateWithFlags(&c->det_ev[k], hipEventDisableTiming));
     }
     auto submit = [&](int o, int slot) {
         std::vector<Frame> fr(frames.begin() + o, frames.begin() + std::min(N, o + batch));
         const int B = (int)fr.size();
-        int* d_counts = c->s_cand2[slot].as<int>();
-        CandRec* d_cands = reinterpret_cast<CandRec*>(c->s_cand2[slot].as<uint8_t>() + cnt_bytes);
+        int* d_counts = dl.counts.in(c->s_cand2[slot]); CandRec* d_cands = dl.cands.in(c->s_cand2[slot]);
         HIP_CHECK(hipMemsetAsync(d_counts, 0, (size_t)(B + SCR_CTL_INTS) * sizeof(int), c->det_stream));
         c->det_slot = slot;
         det_run_batch_ml(c, fr, upsample, sp, d_counts, d_cands);
         HIP_CHECK(hipGetLastError());
-        uint8_t* hb = c->h_cand2[slot].as<uint8_t>();
-        HIP_CHECK(hipMemcpyAsync(hb, d_counts, (size_t)(B + SCR_CTL_INTS) * sizeof(int), hipMemcpyDeviceToHost, c->det_stream));
-        HIP_CHECK(hipMemcpy2DAsync(hb + cnt_bytes, (size_t)PF * sizeof(CandRec), d_cands, (size_t)cap * sizeof(CandRec),
+        HIP_CHECK(hipMemcpyAsync(hl.counts.in(c->h_cand2[slot]), d_counts, (size_t)(B + SCR_CTL_INTS) * sizeof(int), hipMemcpyDeviceToHost, c->det_stream));
+        HIP_CHECK(hipMemcpy2DAsync(hl.cands.in(c->h_cand2[slot]), (size_t)PF * sizeof(CandRec), d_cands, (size_t)cap * sizeof(CandRec),
                                    (size_t)PF * sizeof(CandRec), (size_t)B, hipMemcpyDeviceToHost, c->det_stream));
         HIP_CHECK(hipEventRecord(c->det_ev[slot], c->det_stream));
     };
     auto collect = [&](int o, int slot) {
         const int B = std::min(N, o + batch) - o;
         HIP_CHECK(hipEventSynchronize(c->det_ev[slot]));
-        const uint8_t* hb = c->h_cand2[slot].as<uint8_t>();
-        const int* h_counts = reinterpret_cast<const int*>(hb);
-        const CandRec* h_cands = reinterpret_cast<const CandRec*>(hb + cnt_bytes);
-        const CandRec* d_cands = reinterpret_cast<const CandRec*>(c->s_cand2[slot].as<uint8_t>() + cnt_bytes);
+        const int* h_counts = hl.counts.in(c->h_cand2[slot]); const CandRec* h_cands = hl.cands.in(c->h_cand2[slot]);
+        const CandRec* d_cands = dl.cands.in(c->s_cand2[slot]);
         screen_verdict(c, h_counts + B);
         for (int b = 0; b < B; ++b)
             if (h_counts[b] > cap) {

@@ -992,15 +992,15 @@ static DsstBuffers prepare(Ctx* c, const std::vector<Tracker*>& t, const std::ve
         c->s_trk1.ensure((size_t)n * NPL * FS * FS * sizeof(double2));
         b.F = c->s_trk1.as<double2>();
     }
-    const size_t g = need_F ? (size_t)n * FS * FS * sizeof(double2) : 0, fs = (size_t)n * SDIM * NSC * sizeof(double2);
-    c->s_trk2.ensure(2 * g + fs + (size_t)n * 12 * sizeof(double) + (size_t)n * sizeof(TrkJob) + 256);
-    uint8_t* q = c->s_trk2.as<uint8_t>();
-    b.G0 = reinterpret_cast<double2*>(q); q += g;
-    b.G1 = reinterpret_cast<double2*>(q); q += g;
-    b.Fs = reinterpret_cast<double2*>(q); q += fs;
-    b.results = reinterpret_cast<double*>(q); q += (size_t)n * 8 * sizeof(double);
-    b.pos = reinterpret_cast<double*>(q); q += (size_t)n * 4 * sizeof(double);
-    b.jobs = reinterpret_cast<TrkJob*>(q);
+    ScratchLayout lay;
+    const size_t g = need_F ? (size_t)n * FS * FS : 0;
+    const auto sG0 = lay.take<double2>(g), sG1 = lay.take<double2>(g), sFs = lay.take<double2>((size_t)n * SDIM * NSC);
+    const auto sResults = lay.take<double>((size_t)n * 8), sPos = lay.take<double>((size_t)n * 4);
+    const auto sJobs = lay.take<TrkJob>(n);
+    lay.pad(256);                                             // reason unknown, kept
+    c->s_trk2.ensure(lay.bytes());
+    b.G0 = sG0.in(c->s_trk2); b.G1 = sG1.in(c->s_trk2); b.Fs = sFs.in(c->s_trk2);
+    b.results = sResults.in(c->s_trk2); b.pos = sPos.in(c->s_trk2); b.jobs = sJobs.in(c->s_trk2);
     for (int i = 0; i < n; ++i) jobs[i].pos = b.pos + 4 * (size_t)i;
     void* hj = c->stage.take((size_t)n * sizeof(TrkJob));
     memcpy(hj, jobs.data(), (size_t)n * sizeof(TrkJob));

@@ -105,19 +105,20 @@ void ert_run(Ctx* c, const std::vector<Frame>& frames, const pvf_rect_i32* boxes
         jobs[i].img = frames[i].d; jobs[i].h = frames[i].h; jobs[i].w = frames[i].w;
         jobs[i].rect[0] = boxes[i].left; jobs[i].rect[1] = boxes[i].top; jobs[i].rect[2] = boxes[i].right; jobs[i].rect[3] = boxes[i].bottom;
     }
-    const size_t jb = (size_t)n * sizeof(ErtJob), pb = (size_t)n * s.n_parts * 2 * sizeof(int32_t);
-    c->s_misc.ensure(jb + pb + 64);
-    uint8_t* d_jobs = c->s_misc.as<uint8_t>();
-    int32_t* d_pts = reinterpret_cast<int32_t*>(d_jobs + (jb + 63) / 64 * 64);
-    HIP_CHECK(hipMemcpyAsync(d_jobs, jobs.data(), jb, hipMemcpyHostToDevice, c->stream));
+    ScratchLayout lay;
+    const auto sJobs = lay.take<ErtJob>(n, 64); const auto sPts = lay.take<int32_t>((size_t)n * s.n_parts * 2, 64);
+    lay.pad(64);                                              // reason unknown, kept
+    c->s_misc.ensure(lay.bytes());
+    ErtJob* d_jobs = sJobs.in(c->s_misc); int32_t* d_pts = sPts.in(c->s_misc);
+    HIP_CHECK(hipMemcpyAsync(d_jobs, jobs.data(), sJobs.bytes(), hipMemcpyHostToDevice, c->stream));
     const size_t lds = (size_t)(((2 * s.n_parts + 3) & ~3) + ((s.n_pix + 3) & ~3)) * 4 + (size_t)s.n_trees * 4;
     {
         ProfScope ps(c, "ert");
-        hipLaunchKernelGGL(ert_k, dim3(n), dim3(256), lds, c->stream, reinterpret_cast<const ErtJob*>(d_jobs), s.n_cascades, s.n_trees,
+        hipLaunchKernelGGL(ert_k, dim3(n), dim3(256), lds, c->stream, d_jobs, s.n_cascades, s.n_trees,
                            s.n_parts, s.n_pix, s.depth, s.d_initial, s.d_anchor, s.d_deltas, s.d_idx1, s.d_idx2, s.d_thresh, s.d_leaves,
                            d_pts);
     }
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(pts, d_pts, pb, hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(hipMemcpyAsync(pts, d_pts, sPts.bytes(), hipMemcpyDeviceToHost, c->stream));
     HIP_CHECK(hipStreamSynchronize(c->stream));
 }

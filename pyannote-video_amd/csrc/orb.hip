@@ -448,6 +448,16 @@ std::vector<int> orb_level_quota()
     return q;
 }
 
+// the resident set in s_orb_set: [n][cap] descriptors and keypoints, then the counts.  orb_extract writes it and orb_match_counts finds
+// the descriptors and counts again through the same function (a layout is a function of its arguments alone)
+struct OrbSetLayout { ScratchLayout lay; ScratchSlot<uint8_t> desc; ScratchSlot<Kp> kp; ScratchSlot<int> cnt; };
+static OrbSetLayout orb_set_layout(int n, int cap)
+{
+    OrbSetLayout s;
+    s.desc = s.lay.take<uint8_t>((size_t)n * cap * 32); s.kp = s.lay.take<Kp>((size_t)n * cap); s.cnt = s.lay.take<int>(n);
+    return s;
+}
+
 void orb_extract(Ctx* c, const std::vector<Frame>& frames, int ow, int oh, int cap, int32_t* counts, float* kp_out, uint8_t* desc_out)
 {
     const int n = (int)frames.size();
@@ -475,11 +485,9 @@ void orb_extract(Ctx* c, const std::vector<Frame>& frames, int ow, int oh, int c
         nlev = l + 1;
     }
     pl.nlev = nlev; pl.P = P; pl.C = C;
-    // resident set: [n][cap] keypoints and descriptors, counts
-    c->s_orb_set.ensure(al((size_t)n * cap * 32) + al((size_t)n * cap * sizeof(Kp)) + al((size_t)n * 4));
-    uint8_t* d_desc = c->s_orb_set.as<uint8_t>();
-    Kp* d_kp = reinterpret_cast<Kp*>(d_desc + al((size_t)n * cap * 32));
-    int* d_cnt = reinterpret_cast<int*>(reinterpret_cast<uint8_t*>(d_kp) + al((size_t)n * cap * sizeof(Kp)));
+    const OrbSetLayout set = orb_set_layout(n, cap);
+    c->s_orb_set.ensure(set.lay.bytes());
+    uint8_t* d_desc = set.desc.in(c->s_orb_set); Kp* d_kp = set.kp.in(c->s_orb_set); int* d_cnt = set.cnt.in(c->s_orb_set);
     c->orb_n = 0; c->orb_cap = cap;
     if (nlev == 0) {
         HIP_CHECK(hipMemsetAsync(d_cnt, 0, (size_t)n * 4, c->stream));
@@ -490,23 +498,18 @@ void orb_extract(Ctx* c, const std::vector<Frame>& frames, int ow, int oh, int c
         for (int l = 0; l < nlev; ++l) { tx[l] = tab.size(); tab.insert(tab.end(), cx[l].begin(), cx[l].end()); ty[l] = tab.size(); tab.insert(tab.end(), cy[l].begin(), cy[l].end()); }
         const std::vector<int> pat = random_pattern();
         const int chunk = (int)std::max<long long>(1, std::min<long long>(n, (1ll << 30) / (P * 5 + C * 12 + (long long)kLevels * cap * (sizeof(Kp) + 32))));
-        const size_t tab_bytes = al(tab.size() * sizeof(Coef)), pat_bytes = al(pat.size() * 4), ptr_bytes = al((size_t)n * sizeof(void*));
-        const size_t per = (size_t)P * 5 + (size_t)C * 12 + (size_t)kLevels * cap * (sizeof(Kp) + 32) + kLevels * 4;
-        c->s_misc.ensure(tab_bytes + pat_bytes + ptr_bytes + (size_t)chunk * per + 8 * 256);
-        uint8_t* q = c->s_misc.as<uint8_t>();
-        Coef* d_tab = reinterpret_cast<Coef*>(q); q += tab_bytes;
-        int* d_pat = reinterpret_cast<int*>(q); q += pat_bytes;
-        const uint8_t** d_ptr = reinterpret_cast<const uint8_t**>(q); q += ptr_bytes;
-        uint8_t* d_pyr = q; q += al((size_t)chunk * P);
-        uint8_t* d_score = q; q += al((size_t)chunk * P);
-        uint8_t* d_blur = q; q += al((size_t)chunk * P);
-        uint16_t* d_tmp = reinterpret_cast<uint16_t*>(q); q += al((size_t)chunk * P * 2);
-        uint32_t* d_ca = reinterpret_cast<uint32_t*>(q); q += al((size_t)chunk * C * 4);
-        uint32_t* d_cb = reinterpret_cast<uint32_t*>(q); q += al((size_t)chunk * C * 4);
-        float* d_resp = reinterpret_cast<float*>(q); q += al((size_t)chunk * C * 4);
-        Kp* d_skp = reinterpret_cast<Kp*>(q); q += al((size_t)chunk * kLevels * cap * sizeof(Kp));
-        uint8_t* d_sdesc = q; q += al((size_t)chunk * kLevels * cap * 32);
-        int* d_sn = reinterpret_cast<int*>(q);
+        const size_t cP = (size_t)chunk * P, cC = (size_t)chunk * C, cK = (size_t)chunk * kLevels * cap;
+        ScratchLayout lay;
+        const auto sTab = lay.take<Coef>(tab.size()); const auto sPat = lay.take<int>(pat.size()); const auto sPtr = lay.take<const uint8_t*>(n);
+        const auto sPyr = lay.take<uint8_t>(cP), sScore = lay.take<uint8_t>(cP), sBlur = lay.take<uint8_t>(cP); const auto sTmp = lay.take<uint16_t>(cP);
+        const auto sCa = lay.take<uint32_t>(cC), sCb = lay.take<uint32_t>(cC); const auto sResp = lay.take<float>(cC);
+        const auto sSkp = lay.take<Kp>(cK); const auto sSdesc = lay.take<uint8_t>(cK * 32); const auto sSn = lay.take<int>((size_t)chunk * kLevels);
+        lay.pad(8 * 256);                                     // stood for the rounding of the pieces, which take() now counts; kept so that the buffer does not shrink
+        c->s_misc.ensure(lay.bytes());
+        Coef* d_tab = sTab.in(c->s_misc); int* d_pat = sPat.in(c->s_misc); const uint8_t** d_ptr = sPtr.in(c->s_misc);
+        uint8_t* d_pyr = sPyr.in(c->s_misc); uint8_t* d_score = sScore.in(c->s_misc); uint8_t* d_blur = sBlur.in(c->s_misc); uint16_t* d_tmp = sTmp.in(c->s_misc);
+        uint32_t* d_ca = sCa.in(c->s_misc); uint32_t* d_cb = sCb.in(c->s_misc); float* d_resp = sResp.in(c->s_misc);
+        Kp* d_skp = sSkp.in(c->s_misc); uint8_t* d_sdesc = sSdesc.in(c->s_misc); int* d_sn = sSn.in(c->s_misc);
         std::vector<const uint8_t*> ptrs(n);
         for (int i = 0; i < n; ++i) ptrs[i] = frames[i].d;
         HIP_CHECK(hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(Coef), hipMemcpyHostToDevice, c->stream));
@@ -558,20 +561,20 @@ void orb_match_counts(Ctx* c, const uint8_t* desc, const int32_t* nrows, int n_s
     }
     for (int64_t p = 0; p < 2 * n_pairs; ++p) PVF_REQUIRE(pairs[p] >= 0 && pairs[p] < n_sets, "orb match: a pair names a set that does not exist");
     if (n_pairs == 0) return;
-    const size_t pair_bytes = al((size_t)n_pairs * 8), out_bytes = al((size_t)n_pairs * 4);
-    const size_t own = resident ? 0 : al((size_t)n_sets * cap * 32) + al((size_t)n_sets * 4);
-    c->s_orb_work.ensure(pair_bytes + out_bytes + own + 256);
-    uint8_t* q = c->s_orb_work.as<uint8_t>();
-    int* d_pairs = reinterpret_cast<int*>(q); q += pair_bytes;
-    int* d_out = reinterpret_cast<int*>(q); q += out_bytes;
+    ScratchLayout lay;
+    const auto sPairs = lay.take<int>((size_t)n_pairs * 2), sOut = lay.take<int>(n_pairs);
+    const auto sDesc = lay.take<uint8_t>(resident ? 0 : (size_t)n_sets * cap * 32);       // the sets of this call, when it brings its own
+    const auto sN = lay.take<int>(resident ? 0 : n_sets);
+    lay.pad(256);                                             // reason unknown, kept
+    c->s_orb_work.ensure(lay.bytes());
+    int* d_pairs = sPairs.in(c->s_orb_work); int* d_out = sOut.in(c->s_orb_work);
     const uint8_t* d_desc;
     const int* d_n;
     if (resident) {
-        d_desc = c->s_orb_set.as<uint8_t>();
-        d_n = reinterpret_cast<const int*>(d_desc + al((size_t)c->orb_n * cap * 32) + al((size_t)c->orb_n * cap * sizeof(Kp)));
+        const OrbSetLayout set = orb_set_layout(c->orb_n, c->orb_cap);
+        d_desc = set.desc.in(c->s_orb_set); d_n = set.cnt.in(c->s_orb_set);
     } else {
-        uint8_t* dd = q; q += al((size_t)n_sets * cap * 32);
-        int* dn = reinterpret_cast<int*>(q);
+        uint8_t* dd = sDesc.in(c->s_orb_work); int* dn = sN.in(c->s_orb_work);
         HIP_CHECK(hipMemcpyAsync(dd, desc, (size_t)n_sets * cap * 32, hipMemcpyHostToDevice, c->stream));
         HIP_CHECK(hipMemcpyAsync(dn, nrows, (size_t)n_sets * 4, hipMemcpyHostToDevice, c->stream));
         d_desc = dd; d_n = dn;

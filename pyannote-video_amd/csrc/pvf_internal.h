@@ -14,10 +14,10 @@
 #include <unordered_map>
 #include <vector>
 #include "../../include/pvface.h"
+#include "scratch_layout.h"      // PvfError, ScratchLayout
 
 #define PVF_FHOG_STRIDE 32
 
-struct PvfError : std::runtime_error { using std::runtime_error::runtime_error; };
 // a frame produced more raw candidates than the context's candidate slots hold: the entry point enlarges them and runs the call again
 struct CandOverflow : PvfError { int needed; explicit CandOverflow(int n) : PvfError("detector: candidate buffer overflow"), needed(n) {} };
 // the screening pass (screen.hip) listed more windows than its list holds, or met a feature above the bound its error analysis assumes:
@@ -431,5 +431,7 @@ struct PairOutput { double* out = nullptr; bool on_device = false; bool compact 
 void pair_mean_dist_dev(Ctx* c, const PairInput& in, int N, int dim, const int32_t* row_start, int T, const PairOutput& out, double** d_D_keep,
                         int t0, int t1, int metric, bool mirror);
 void mirror_upper_dev(Ctx* c, double* dD, int T);
+// the T x T distance matrix in s_clu1 (one array, so no layout).  Tail of 64 bytes per track + 4096: reason unknown, kept
+inline size_t dist_matrix_bytes(int T) { return (size_t)T * T * sizeof(double) + (size_t)T * 64 + 4096; }
 int hac_dev(Ctx* c, double* d_D, const int32_t* row_start, int T, double threshold, int32_t* labels, double* merge_log,
             const double* extent = nullptr, int32_t* n_blocked = nullptr, int flags = 0);

@@ -332,17 +332,17 @@ void shot_dfd(Ctx* c, const std::vector<Frame>& frames, int ow, int oh, const fl
     cv_coeffs(ih, oh, cy);
     cv_coeffs(iw, ow, cx);
     const size_t stride = (size_t)px * (1 + 1 + 2 + 3 + 10 + 5 + 5 + 4);
-    const size_t coef_bytes = ((size_t)(oh + ow) * sizeof(Coef) + 255) / 256 * 256, ptr_bytes = ((size_t)n * sizeof(void*) + 255) / 256 * 256;
-    const size_t gray_bytes = ((size_t)n * px + 255) / 256 * 256, dfd_bytes = ((size_t)n * sizeof(double) + 255) / 256 * 256;
     const size_t flow_bytes = flow_out ? (size_t)(n - 1) * px * 2 * sizeof(float) : 0;
-    c->s_misc.ensure(coef_bytes + ptr_bytes + gray_bytes + dfd_bytes + flow_bytes + (size_t)std::max(n - 1, 1) * stride * sizeof(float) + 256);
-    uint8_t* q = c->s_misc.as<uint8_t>();
-    Coef* d_coef = reinterpret_cast<Coef*>(q); q += coef_bytes;
-    const uint8_t** d_ptr = reinterpret_cast<const uint8_t**>(q); q += ptr_bytes;
-    uint8_t* d_gray = q; q += gray_bytes;
-    double* d_dfd = reinterpret_cast<double*>(q); q += dfd_bytes;
-    float* d_flow = flow_out ? reinterpret_cast<float*>(q) : nullptr; q += flow_bytes;
-    float* d_scratch = reinterpret_cast<float*>(q);
+    ScratchLayout lay;
+    const auto sCoef = lay.take<Coef>(oh + ow); const auto sPtr = lay.take<const uint8_t*>(n);
+    const auto sGray = lay.take<uint8_t>((size_t)n * px); const auto sDfd = lay.take<double>(n);
+    const auto sFlow = lay.take<float>(flow_bytes / sizeof(float)), sScratch = lay.take<float>((size_t)std::max(n - 1, 1) * stride);
+    lay.pad(256);                                             // reason unknown, kept
+    c->s_misc.ensure(lay.bytes());
+    Coef* d_coef = sCoef.in(c->s_misc); const uint8_t** d_ptr = sPtr.in(c->s_misc);
+    uint8_t* d_gray = sGray.in(c->s_misc); double* d_dfd = sDfd.in(c->s_misc);
+    float* d_flow = flow_out ? sFlow.in(c->s_misc) : nullptr;
+    float* d_scratch = sScratch.in(c->s_misc);
     std::vector<Coef> both(cy);
     both.insert(both.end(), cx.begin(), cx.end());
     std::vector<const uint8_t*> ptrs(n);

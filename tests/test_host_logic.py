@@ -506,6 +506,24 @@ def test_hac_quotient_by_reciprocal_is_the_ieee_quotient(tmp_path):
     assert " 0 differ" in out.stdout
 
 
+def test_scratch_layout_slots_are_disjoint_aligned_and_inside(tmp_path):
+    """csrc/scratch_layout.h, which sizes and carves every shared scratch buffer: slots of mixed types, alignments and counts are disjoint,
+    aligned and inside bytes(); their first and last bytes are writable in a buffer of exactly bytes(); pad adds what was asked; in() refuses
+    a buffer that is too small; the same arguments give the same offsets (tests/csrc/scratch_layout_check.cpp, under ASan + UBSan)"""
+    import shutil
+    import subprocess
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    here = os.path.dirname(os.path.abspath(__file__))
+    exe = str(tmp_path / "scratch_layout_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-I", os.path.join(here, "..", "pyannote-video_amd", "csrc"), "-o", exe,
+                           os.path.join(here, "csrc", "scratch_layout_check.cpp")])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, (out.stdout[-800:], out.stderr[-800:])
+    assert "0 failures" in out.stdout
+
+
 def test_parse_rows_returns_what_loadtxt_returns():
     """pvf_parse_rows (the embedding.txt reader behind FaceClustering's preprocess) against np.loadtxt: the writers' 5-decimal rows bit for
     bit, exponents / inf / nan / long digit strings through strtod, blank lines skipped, ragged rows and non-numbers refused"""
