@@ -359,6 +359,33 @@ int32_t pvf_pair_upper_rows_f32(pvf_handle ctx, const float* emb, int64_t row_st
                                 const int32_t* order, int32_t N, int32_t decimals, const int32_t* row_start, int32_t T,
                                 int32_t track0, int32_t track1, double* rows_out, int32_t out_on_device);
 
+/* ---- identification against a gallery ----------------------------------------------------------------------------------------------
+ * WHO a face is: query rows X float64 [N][dim] in T groups (row_start[T+1]; a group is a track or a cluster), gallery rows G float64
+ * [M][dim] in K identities (gal_start[K+1]: the enrolled descriptors of each known person).  There is NO REFERENCE CALL: naming a 128-D
+ * descriptor by its distance to known faces is the use the embedder was trained for ("below 0.6 is the same person"), the reference
+ * offers none.  The measure is the one pvf_cluster_tracks merges by: a group belongs to an identity when the MEAN PAIRWISE DISTANCE
+ * between its rows and the identity's rows is at most `threshold` -- one more average-linkage step against fixed, named clusters.
+ * `metric` and `threshold` mean what they mean in pvf_cluster_tracks / pvf_pair_mean_dist_metric (0 Euclidean, 1 cosine distance,
+ * 0 where a norm is 0; `<=`; the default of the callers is 0.6).
+ *   D[t][k]  = mean over the rows i of group t and the rows j of identity k of dist(x_i, g_j), float64, T x K row-major, computed on the
+ *              f64 matrix cores by the rectangular form of K10; neither N x M nor N x K is materialised.  Defined up to rounding
+ *              (rtol 1e-12 Euclidean, 1e-10 cosine), not bit for bit: the additions that form an entry depend on where the rows of the
+ *              group and of the identity fall in their 16-row blocks.  The same call returns the same bits.
+ *   decision per group t: an entry is TAKEN when it is below +inf (NaN and +inf entries are never taken).  best = the index of the first
+ *              minimum of row t among the taken entries (the lowest k wins on equal values); second = the first minimum over k != best.
+ *              A row with nothing to take gives (-1, +inf); with K = 1 the second is (-1, +inf).  Then best = -1 unless
+ *              best_dist <= threshold (NaN is refused as a threshold); best_dist keeps the measured value either way.
+ * Checked on the host before any device work: T, K >= 1; dim == 128; row_start and gal_start start at 0, are non-decreasing, have no
+ * empty group and end at N and M; sizes that 32-bit offsets cannot address (2^30 rows, an identity of 2^20 rows) are refused.
+ * pvf_identify_dist: the decision alone, on a host matrix.  pvf_identify: both, D stays in HBM in between; D (T x K, host) may be NULL. */
+int32_t pvf_gallery_mean_dist(pvf_handle ctx, const double* X, int32_t N, const int32_t* row_start, int32_t T, const double* G, int32_t M,
+                              const int32_t* gal_start, int32_t K, int32_t dim, int32_t metric, double* D /* T x K, host */);
+int32_t pvf_identify_dist(pvf_handle ctx, const double* D, int32_t T, int32_t K, double threshold, int32_t* best, double* best_dist,
+                          int32_t* second, double* second_dist);
+int32_t pvf_identify(pvf_handle ctx, const double* X, int32_t N, const int32_t* row_start, int32_t T, const double* G, int32_t M,
+                     const int32_t* gal_start, int32_t K, int32_t dim, int32_t metric, double threshold, int32_t* best, double* best_dist,
+                     int32_t* second, double* second_dist, double* D /* T x K host, or NULL */);
+
 /* ---- file formats (host) ------------------------------------------------------------------------------ */
 /* ref: scripts/pyannote-face.py:299-311  the lines of landmarks.txt / embedding.txt: "{t:.3f} {identifier:d}" + n_cols x " {v:.<decimals>f}"
  * + newline per row, byte for byte what Python's format writes (both are the correctly rounded decimal).  values [n_rows][n_cols];

@@ -1062,6 +1062,43 @@ extern "C" int32_t pvf_format_rows(const double* t, const int64_t* identifier, c
 // float64 value of its 5-decimal text.  In memory: x (float32) -> double -> np.round(x, 5), which numpy evaluates as rint(x * 1e5) / 1e5
 // (three correctly rounded double operations; the same three here, on a few threads -- numpy's own np.round spends 10-28 ms on 8000 x 128
 // values, at the very end of a run, when the GPU has nothing left to do).
+// ---- identification against a gallery (identify.hip) -------------------------------------------------------------------------------
+extern "C" int32_t pvf_gallery_mean_dist(pvf_handle h, const double* X, int32_t N, const int32_t* row_start, int32_t T, const double* G, int32_t M,
+                                         const int32_t* gal_start, int32_t K, int32_t dim, int32_t metric, double* D)
+{
+    API_BEGIN
+    ENTER(c, h);
+    PVF_REQUIRE(X && G && D, "pvf_gallery_mean_dist: bad arguments");
+    identify_check_dist("pvf_gallery_mean_dist", N, row_start, T, M, gal_start, K, dim, metric);
+    gallery_mean_dist_dev(c, X, N, row_start, T, G, M, gal_start, K, metric, D);
+    API_END
+}
+
+extern "C" int32_t pvf_identify_dist(pvf_handle h, const double* D, int32_t T, int32_t K, double threshold, int32_t* best, double* best_dist,
+                                     int32_t* second, double* second_dist)
+{
+    API_BEGIN
+    ENTER(c, h);
+    PVF_REQUIRE(D && best && best_dist && second && second_dist, "pvf_identify_dist: bad arguments");
+    identify_check_pick("pvf_identify_dist", T, K, threshold);
+    identify_pick_dev(c, nullptr, D, T, K, threshold, best, best_dist, second, second_dist);
+    API_END
+}
+
+extern "C" int32_t pvf_identify(pvf_handle h, const double* X, int32_t N, const int32_t* row_start, int32_t T, const double* G, int32_t M,
+                                const int32_t* gal_start, int32_t K, int32_t dim, int32_t metric, double threshold, int32_t* best,
+                                double* best_dist, int32_t* second, double* second_dist, double* D)
+{
+    API_BEGIN
+    ENTER(c, h);
+    PVF_REQUIRE(X && G && best && best_dist && second && second_dist, "pvf_identify: bad arguments");
+    identify_check_dist("pvf_identify", N, row_start, T, M, gal_start, K, dim, metric);
+    identify_check_pick("pvf_identify", T, K, threshold);
+    const double* dD = gallery_mean_dist_dev(c, X, N, row_start, T, G, M, gal_start, K, metric, D);      // (D stays in HBM for the decision)
+    identify_pick_dev(c, dD, nullptr, T, K, threshold, best, best_dist, second, second_dist);
+    API_END
+}
+
 extern "C" int32_t pvf_round_rows(const float* x, int64_t n, int32_t decimals, double* out)
 {
     API_BEGIN

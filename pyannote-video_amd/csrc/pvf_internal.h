@@ -435,3 +435,11 @@ void mirror_upper_dev(Ctx* c, double* dD, int T);
 inline size_t dist_matrix_bytes(int T) { return (size_t)T * T * sizeof(double) + (size_t)T * 64 + 4096; }
 int hac_dev(Ctx* c, double* d_D, const int32_t* row_start, int T, double threshold, int32_t* labels, double* merge_log,
             const double* extent = nullptr, int32_t* n_blocked = nullptr, int flags = 0);
+// identification against a gallery (identify.hip): the checks of a call (host, before any device work), the T x K block means
+// (left in s_clu1 and returned; also copied to D_host when given), and the decision per group on a device or a host matrix
+void identify_check_dist(const char* who, int N, const int32_t* row_start, int T, int M, const int32_t* gal_start, int K, int dim, int metric);
+void identify_check_pick(const char* who, int T, int K, double threshold);
+double* gallery_mean_dist_dev(Ctx* c, const double* X, int N, const int32_t* row_start, int T, const double* G, int M, const int32_t* gal_start,
+                              int K, int metric, double* D_host);
+void identify_pick_dev(Ctx* c, const double* d_D, const double* D_host, int T, int K, double threshold, int32_t* best, double* best_dist,
+                       int32_t* second, double* second_dist);

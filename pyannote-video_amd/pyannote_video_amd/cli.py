@@ -6,11 +6,16 @@
     python -m pyannote_video_amd process [options] <video> <shot.json> <landmark_model> <embedding_model> <tracking> <landmarks> <embeddings>
     python -m pyannote_video_amd shot    [options] <video> <output.json>
     python -m pyannote_video_amd thread  [--min-match 20] [--lookahead 24] <video> <shot.json> <output.json>
+    python -m pyannote_video_amd enroll  [--append] <video> <landmark_model> <embedding_model> <name> <gallery>
+    python -m pyannote_video_amd enroll-track [--append] <embeddings> <track> <name> <gallery>
+    python -m pyannote_video_amd identify [--threshold 0.6] [--metric euclidean|cosine] [--labels PATH] [--unknown NAME] [--scores PATH] <embeddings> <gallery> <output>
     python -m pyannote_video_amd demo    [--height 400] [--from 0] [--until T] [--shift 0] [--landmark PATH] [--label PATH] <video> <tracking> <output>
 
 `track` and `extract` take the reference's arguments and options and write byte-compatible files (track.txt, landmarks.txt,
 embedding.txt: formats.py).  `cluster` is the verb BASELINE.json's north_star names; the reference offers clustering through the API
 only (face/clustering.py:130-134).  It writes `identifier label` lines, the file `demo --label` reads (pyannote-face.py:87,391-397).
+`enroll` / `enroll-track` / `identify` (identification.py; no reference verb) name tracks or clusters against a gallery of enrolled faces:
+`identify` writes `identifier name` lines, the same file `demo --label` reads; `process --gallery` does it in the same run.
 `demo` (pyannote-face.py:317-413) writes the video with the tracks, their numbers and labels and, with --landmark, the nose lines drawn
 on it, as a YUV4MPEG2 stream: to a `.y4m` path, or to stdout for `-` (`... demo film.y4m track.txt - | ffmpeg -i - out.mp4`).  Resize,
 drawing and RGB -> YUV 4:2:0 run in one kernel on the GPU (DEMO.md states every pixel; the font is the project's own, not OpenCV's
@@ -250,10 +255,14 @@ def extract(video, landmark_model, embedding_model, tracking, landmark_output, e
 
 def process(video, shot, landmark_model, embedding_model, tracking_output, landmark_output, embedding_output, label_output=None,
             detect_min_size=0.0, detect_every=0.0, track_min_overlap_ratio=MIN_OVERLAP_RATIO, track_min_confidence=MIN_CONFIDENCE,
-            track_max_gap=MAX_GAP, threshold=0.6, ctx=None, do_not_cooccur=False):
+            track_max_gap=MAX_GAP, threshold=0.6, ctx=None, do_not_cooccur=False, gallery=None, identify_threshold=0.6, unknown=None):
     """`track` + `extract` (+ `cluster`) in ONE pass over the video -- one decode, one upload per frame; the reference needs two decodes
     (pyannote-face.py:261 and :287).  Writes the same three files as the separate verbs, line for line (the faces of one frame in the
-    order pandas' sort of the complete track table gives them: formats.file_order), plus the `identifier label` file of `cluster`."""
+    order pandas' sort of the complete track table gives them: formats.file_order), plus the `identifier label` file of `cluster`.
+    gallery (needs label_output): the clusters are identified from the rows the run itself produced, the labels file carries names for
+    the matched clusters and cluster numbers for the rest -- exactly what `identify --labels` writes from the files of the same run."""
+    if gallery is not None and label_output is None:
+        raise ValueError("process: --gallery names clusters, it needs --labels")
     pipe = _pipeline(video, ctx, landmark_model, embedding_model, detect_min_size=detect_min_size, detect_every=detect_every,
                      track_min_overlap_ratio=track_min_overlap_ratio, track_min_confidence=track_min_confidence, track_max_gap=track_max_gap,
                      threshold=threshold, constraint="cooccur" if do_not_cooccur else None)
@@ -273,10 +282,22 @@ def process(video, shot, landmark_model, embedding_model, tracking_output, landm
     with open(landmark_output, 'wb') as flandmark, open(embedding_output, 'wb') as fembedding:
         flandmark.write(formats.landmark_rows(res["face_T"], res["face_id"], res["landmarks"], w, h))
         fembedding.write(formats.embedding_rows(res["face_T"], res["face_id"], res["embeddings"]))
-    if label_output is not None:
+    if label_output is not None and gallery is None:
         with open(label_output, 'w') as f:
             for identifier in sorted(set(res["face_id"].tolist())):
                 f.write('{identifier:d} {label:d}\n'.format(identifier=identifier, label=res["labels"].get(identifier, identifier)))
+    elif label_output is not None:
+        from . import identification, _lib
+        tracks = sorted(set(res["face_id"].tolist()))
+        label = {t: int(res["labels"].get(t, t)) for t in tracks}
+        res["identification"] = []
+        if tracks:
+            # the rows as `identify` reads them back from the files written above: 3-decimal times, 5-decimal values, file order
+            T = np.array([formats.quantise_time(t) for t in res["face_T"]], np.float64)
+            X = res["X"] if res.get("X") is not None else _lib.round_rows(res["embeddings"], 5)
+            ident = identification.FaceIdentification(gallery, threshold=identify_threshold, ctx=pipe.ctx)
+            res["identification"] = ident.scores_arrays(res["face_id"], X, label, T)
+        identification.write_identification(label_output, res["identification"], tracks, label, unknown, per_cluster=True)
     return res
 
 
@@ -298,6 +319,75 @@ def cluster(embeddings, output, threshold=0.6, force=False, metric="euclidean", 
         for identifier in sorted(set(int(t) for t in np.unique(features.track))):
             f.write('{identifier:d} {label:d}\n'.format(identifier=identifier, label=label.get(identifier, identifier)))
     return label
+
+
+def identify(embeddings, gallery, output, threshold=0.6, metric="euclidean", labels=None, unknown=None, scores=None, ctx=None):
+    """Names for the tracks of an embedding file -> `identifier name` lines for `demo --label`.  Without `labels` the decision is made
+    per track: a track nobody matches is left out (or gets `unknown`).  With `labels` (a `cluster` output) it is made per cluster: every
+    track of a matched cluster gets the name, a track of an unmatched one keeps its cluster label (or gets `unknown`), and the file
+    replaces the `cluster` file.  scores: one line per group, `group best_name best_dist second_name second_dist` -- the nearest
+    identity even above the threshold, `-` for a missing name."""
+    from . import identification
+    ident = identification.FaceIdentification(gallery, threshold=threshold, metric=metric, ctx=ctx)
+    time, track, X = formats.read_embeddings(embeddings)
+    label = identification.read_label_map(labels) if labels is not None else {}
+    result = ident.scores_arrays(track, X, label or None, time)
+    identification.write_identification(output, result, np.unique(track).tolist(), label, unknown, per_cluster=labels is not None,
+                                        scores_output=scores)
+    return {g: (name if matched else None, bd, second, sd) for g, name, bd, second, sd, matched in result}
+
+
+def enroll_track(embeddings, track, name, gallery, append=False):
+    """the rows of one track of an embedding file, under a name: how a person who appears in the video gets enrolled"""
+    from . import identification
+    formats.check_gallery_name(name)
+    _, ids, X = formats.read_embeddings(embeddings)
+    rows = X[ids == int(track)]
+    if len(rows) == 0:
+        raise ValueError("%s has no row of track %d" % (embeddings, int(track)))
+    identification.FaceGallery().add(name, rows).save(gallery, append=append)
+    return len(rows)
+
+
+def enroll(video, landmark_model, embedding_model, name, gallery, append=False, ctx=None, batch=16):
+    """Every frame of the video through detector -> landmarks -> embedder; the detection of largest area is enrolled (the first in
+    detector order on equal areas), frames without a face are skipped.  -> {"faces": enrolled, "skipped": frames without a face}"""
+    import os
+    from . import identification, runtime
+    formats.check_gallery_name(name)
+    if not append and os.path.exists(gallery):
+        raise FileExistsError("%s exists: --append adds to it" % gallery)          # before any work
+    ctx = ctx or runtime.default_context()
+    ctx.load_shape_predictor(landmark_model)
+    ctx.load_embedder(embedding_model)
+    rows, skipped, pending = [], 0, []
+
+    def flush():
+        frames = [ctx.upload(rgb) for rgb in pending]
+        try:
+            keep_f, keep_b = [], []
+            for f, (boxes, _) in zip(frames, ctx.detect_batch(frames, 1)):
+                if boxes:
+                    area = [(b[2] - b[0] + 1) * (b[3] - b[1] + 1) for b in boxes]
+                    keep_f.append(f); keep_b.append(boxes[area.index(max(area))])
+            if keep_b:
+                rows.append(ctx.landmarks_embed(keep_f, keep_b)[1])
+            return len(frames) - len(keep_b)
+        finally:
+            for f in frames:
+                f.release()
+            del pending[:]
+    for _, rgb in video:
+        pending.append(rgb)
+        if len(pending) >= batch:
+            skipped += flush()
+    if pending:
+        skipped += flush()
+    if not rows:
+        raise ValueError("enroll: no face was found in the video")
+    E = np.concatenate(rows)
+    identification.FaceGallery().add(name, E).save(gallery, append=append)
+    return {"faces": int(len(E)), "skipped": int(skipped)}
 
 
 def shot(video, output, height=50, window=2.0, threshold=1.0, ctx=None):
@@ -452,6 +542,9 @@ def _parser():
     pr.add_argument("--max-gap", type=float, default=MAX_GAP)
     pr.add_argument("--threshold", type=float, default=0.6)
     pr.add_argument("--do-not-cooccur", action="store_true", help="tracks on screen at the same time never share a label")
+    pr.add_argument("--gallery", default=None, help="a gallery file of `enroll`: matched clusters get names in the --labels file")
+    pr.add_argument("--identify-threshold", type=float, default=0.6)
+    pr.add_argument("--unknown", default=None, help="the name written for clusters nobody matches (default: their cluster number)")
     s = sub.add_parser("shot")
     s.add_argument("video"); s.add_argument("output")
     s.add_argument("--height", type=int, default=50, help="height of the images the optical flow runs on (reference default 50: one pyramid level; "
@@ -469,6 +562,20 @@ def _parser():
     c.add_argument("--metric", choices=("euclidean", "cosine"), default="euclidean")
     c.add_argument("--do-not-cooccur", action="store_true", help="tracks on screen at the same time never share a label "
                    "(the constraint face/clustering.py:142 names and leaves off)")
+    i = sub.add_parser("identify", help="names for tracks (or, with --labels, clusters) against a gallery of enrolled faces")
+    i.add_argument("embeddings"); i.add_argument("gallery"); i.add_argument("output")
+    i.add_argument("--threshold", type=float, default=0.6, help="largest mean pairwise distance that is still the same person")
+    i.add_argument("--metric", choices=("euclidean", "cosine"), default="euclidean")
+    i.add_argument("--labels", default=None, help="`identifier label` lines of `cluster`: decide per cluster, write a complete replacement")
+    i.add_argument("--unknown", default=None, help="the name written where nobody matches")
+    i.add_argument("--scores", default=None, help="write `group best_name best_dist second_name second_dist` per group")
+    en = sub.add_parser("enroll", help="the largest face of every frame of a video, under a name, into a gallery file")
+    for name in ("video", "landmark_model", "embedding_model", "name", "gallery"):
+        en.add_argument(name)
+    en.add_argument("--append", action="store_true", help="add to an existing gallery file (refused otherwise)")
+    et = sub.add_parser("enroll-track", help="the rows of one track of an embedding file, under a name, into a gallery file")
+    et.add_argument("embeddings"); et.add_argument("track", type=int); et.add_argument("name"); et.add_argument("gallery")
+    et.add_argument("--append", action="store_true")
     d = sub.add_parser("demo", help="the video with tracks, labels and landmarks drawn on it, as YUV4MPEG2")
     d.add_argument("video"); d.add_argument("tracking"); d.add_argument("output", help="a .y4m path, or - for stdout")
     d.add_argument("--height", type=int, default=400, help="height of the output frames; the width keeps the aspect")
@@ -508,9 +615,18 @@ def main(argv=None):
         res = track(video(), a.shot, a.tracking, detect_min_size=a.min_size, detect_every=a.every,
                     track_min_overlap_ratio=a.min_overlap, track_min_confidence=a.min_confidence, track_max_gap=a.max_gap, ctx=ctx)
     elif a.verb == "process":
+        if a.gallery is not None and a.labels is None:
+            ap.error("--gallery names clusters: it needs --labels")
         res = process(video(), a.shot, a.landmark_model, a.embedding_model, a.tracking, a.landmarks, a.embeddings, a.labels,
                 detect_min_size=a.min_size, detect_every=a.every, track_min_overlap_ratio=a.min_overlap,
-                track_min_confidence=a.min_confidence, track_max_gap=a.max_gap, threshold=a.threshold, ctx=ctx, do_not_cooccur=a.do_not_cooccur)
+                track_min_confidence=a.min_confidence, track_max_gap=a.max_gap, threshold=a.threshold, ctx=ctx, do_not_cooccur=a.do_not_cooccur,
+                gallery=a.gallery, identify_threshold=a.identify_threshold, unknown=a.unknown)
+    elif a.verb == "identify":
+        identify(a.embeddings, a.gallery, a.output, threshold=a.threshold, metric=a.metric, labels=a.labels, unknown=a.unknown, scores=a.scores, ctx=ctx)
+    elif a.verb == "enroll":
+        res = enroll(video(), a.landmark_model, a.embedding_model, a.name, a.gallery, append=a.append, ctx=ctx)
+    elif a.verb == "enroll-track":
+        enroll_track(a.embeddings, a.track, a.name, a.gallery, append=a.append)
     elif a.verb == "shot":
         shot(video(), a.output, height=a.height, window=a.window, threshold=a.threshold, ctx=ctx)
     elif a.verb == "thread":

@@ -149,3 +149,41 @@ def read_embeddings(path):
     if data.shape[0] == 0:
         return np.zeros(0), np.zeros(0, np.int64), np.zeros((0, 128))
     return data[:, 0].copy(), data[:, 1].astype(np.int64), np.ascontiguousarray(data[:, 2:])
+
+
+# ---- the gallery of `enroll` / `identify`: one enrolled face per line, "name v0 ... v127", the values as embedding.txt writes them
+def check_gallery_name(name):
+    """a name is one token: `identifier name` lines (what `identify` writes, `demo --label` reads) are split at whitespace"""
+    if not isinstance(name, str) or not name or name.split() != [name]:
+        raise ValueError("gallery: a name must be one token without whitespace, found %r" % (name,))
+    return name
+
+
+def gallery_line(name, embedding):
+    s = check_gallery_name(name)
+    if len(embedding) != 128:
+        raise ValueError("gallery: a face is 128 values, found %d" % len(embedding))
+    for x in embedding:
+        s += ' {x:.5f}'.format(x=float(x))
+    return s + '\n'
+
+
+def read_gallery(path):
+    """-> (names[K], gal_start int32 [K+1], G float64 [M,128]): the lines grouped by name, the names in the order of their first
+    appearance, a name's faces in file order"""
+    faces = {}
+    with open(path) as f:
+        for number, line in enumerate(f, 1):
+            p = line.split()
+            if not p:
+                continue
+            if len(p) != 129:
+                raise ValueError("%s:%d: expected a name and 128 values, found %d tokens" % (path, number, len(p)))
+            try:
+                faces.setdefault(p[0], []).append([float(v) for v in p[1:]])
+            except ValueError:
+                raise ValueError("%s:%d: a value that is not a number" % (path, number))
+    names = list(faces)
+    counts = [len(faces[n]) for n in names]
+    G = np.array([row for n in names for row in faces[n]], np.float64).reshape(-1, 128)
+    return names, np.concatenate([[0], np.cumsum(counts)]).astype(np.int32), G

@@ -874,6 +874,47 @@ class Context(object):
         check(self._l.pvf_pair_mean_dist_metric(self._h, ptr(X), X.shape[0], X.shape[1], ptr(rs), T, int(metric), ptr(D)))
         return D
 
+    # ---- identification against a gallery (pvf_gallery_mean_dist / pvf_identify_dist / pvf_identify; include/pvface.h states the rules)
+    @staticmethod
+    def _identify_tables(X, row_start, G, gal_start):
+        X = np.ascontiguousarray(X, np.float64)
+        G = np.ascontiguousarray(G, np.float64)
+        if X.ndim != 2 or G.ndim != 2 or X.shape[1] != G.shape[1]:
+            raise ValueError("identify: X [N, dim] and G [M, dim] are expected")
+        return X, np.ascontiguousarray(row_start, np.int32), G, np.ascontiguousarray(gal_start, np.int32)
+
+    def gallery_mean_dist(self, X, row_start, G, gal_start, metric=0):
+        """T x K matrix of the mean pair distances between the rows of query group t and the rows of identity k"""
+        X, rs, G, gs = self._identify_tables(X, row_start, G, gal_start)
+        T, K = len(rs) - 1, len(gs) - 1
+        D = np.zeros((max(T, 0), max(K, 0)), np.float64)
+        check(self._l.pvf_gallery_mean_dist(self._h, ptr(X), X.shape[0], ptr(rs), T, ptr(G), G.shape[0], ptr(gs), K, X.shape[1], int(metric), ptr(D)))
+        return D
+
+    @staticmethod
+    def _picks(T):
+        T = max(T, 0)
+        return np.full(T, -1, np.int32), np.full(T, np.inf, np.float64), np.full(T, -1, np.int32), np.full(T, np.inf, np.float64)
+
+    def identify_dist(self, D, threshold):
+        """the decision per row of a T x K matrix -> (best, best_dist, second, second_dist)"""
+        D = np.ascontiguousarray(D, np.float64)
+        if D.ndim != 2:
+            raise ValueError("identify_dist: a T x K matrix is expected")
+        out = self._picks(D.shape[0])
+        check(self._l.pvf_identify_dist(self._h, ptr(D), D.shape[0], D.shape[1], float(threshold), *[ptr(o) for o in out]))
+        return out
+
+    def identify(self, X, row_start, G, gal_start, threshold, metric=0, return_dist=False):
+        """distances and decision in one call -> (best, best_dist, second, second_dist), with return_dist also D [T, K]"""
+        X, rs, G, gs = self._identify_tables(X, row_start, G, gal_start)
+        T, K = len(rs) - 1, len(gs) - 1
+        out = self._picks(T)
+        D = np.zeros((max(T, 0), max(K, 0)), np.float64) if return_dist else None
+        check(self._l.pvf_identify(self._h, ptr(X), X.shape[0], ptr(rs), T, ptr(G), G.shape[0], ptr(gs), K, X.shape[1], int(metric), float(threshold),
+                                   *([ptr(o) for o in out] + [None if D is None else ptr(D)])))
+        return out + (D,) if return_dist else out
+
     # The four agglomerating calls have a `_cooccur` sibling that takes `extent` (float64 [T, 2]: start and end of every track, seconds):
     # the do-not-cooccur constraint (clustering.py:142-143; pvf_cluster_*_cooccur) -- tracks whose extents intersect never share a
     # cluster.  They return (labels, merge log, n_blocked = the co-occurring pairs); `flags` bit 0 is the library's test switch
