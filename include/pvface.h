@@ -252,6 +252,36 @@ int32_t pvf_embed_chips(pvf_handle ctx, const uint8_t* chips, int32_t n, float* 
 /* the aligned chips alone (get_face_chip_details + extract_image_chips), for testing K6 in isolation */
 int32_t pvf_face_chips(pvf_handle ctx, const pvf_handle* frames, const int32_t* pts, int32_t n, uint8_t* chips /* n*150*150*3 */);
 
+/* ---- num_jitters (JITTER.md) ------------------------------------------------------------------------
+ * dlib: compute_face_descriptor(img, shape, num_jitters) -- the descriptor is the fp32 mean of the network's outputs on J = num_jitters
+ * perturbed copies of the aligned chip (shift, zoom, rotation, mirror).  The transform of jitter j is a function of (seed, j) alone,
+ * the same for every face of every call.  J of 0 or 1: the plain descriptor, through the plain entry.  J < 0 and J > 4096 are refused.
+ * Faces go through in rounds of max(1, 4096 / J); the environment variable PVF_JITTER_CHUNK (chips per round, read at the call) lowers
+ * that without changing a bit of the result. */
+#define PVF_JITTER_ROW 17
+/* ref: compute_face_descriptor(img, shape, num_jitters).  Host only (no context, no device): the J transforms.  Row j, 17 doubles:
+ *   [0..3] l t r b   the chip_details rectangle on the 150 x 150 chip      [4] cs = cos(angle)   [5] sn = sin(angle)
+ *   [6]    flip      1.0: output column c takes extracted column 149 - c
+ *   [7..10] m[4], [11..12] b[2]   the sampling affine: px = m0 c + m1 r + b0, py = m2 c + m3 r + b1, relative to (bx0, by0)
+ *   [13..16] bx0 by0 sw sh        the clipped, grown bounding box the black-outside test is relative to */
+int32_t pvf_jitter_plan(int32_t J, uint64_t seed, double* out /* J*17 */);
+/* ref: compute_face_descriptor(img, shape, num_jitters) -- dlib's jitter_image alone: host chips [n][150][150][3] in, the n*J jittered
+ * chips [n][J][150][150][3] out (jitter_k), for testing the step in isolation; J >= 1 */
+int32_t pvf_debug_jitter_chips(pvf_handle ctx, const uint8_t* chips, int32_t n, int32_t J, uint64_t seed, uint8_t* out);
+/* ref: compute_face_descriptor(img, shape, num_jitters) -- a measurement switch: the same sampling by transform_k launched over n*J
+ * jobs on the chips in HBM (profiling family "jitter_xf"; jitter_k's is "jitter").  transform_k has no mirror: jitters with flip = 1
+ * come out unmirrored, everything else is pvf_debug_jitter_chips' output.  out may be NULL: the kernels run, nothing is copied out. */
+int32_t pvf_debug_jitter_chips_transform(pvf_handle ctx, const uint8_t* chips, int32_t n, int32_t J, uint64_t seed, uint8_t* out);
+/* ref: compute_face_descriptor(img, shape, num_jitters) -- pvf_embed with jitters; J <= 1 returns pvf_embed's bits */
+int32_t pvf_embed_jitter(pvf_handle ctx, const pvf_handle* frames, const int32_t* pts /* n*68*2 */, int32_t n, int32_t J, uint64_t seed,
+                         float* out /* n*128 */);
+/* ref: compute_face_descriptor(img, shape, num_jitters) -- pvf_landmarks_embed with jitters (same results as pvf_landmarks followed by
+ * pvf_embed_jitter); J <= 1 returns pvf_landmarks_embed's bits */
+int32_t pvf_landmarks_embed_jitter(pvf_handle ctx, const pvf_handle* frames, const pvf_rect_i32* boxes, int32_t n, int32_t J,
+                                   uint64_t seed, int32_t* pts /* n*68*2 */, float* out /* n*128 */);
+/* ref: compute_face_descriptor(img, shape, num_jitters) -- pvf_embed_chips with jitters (host chips); J <= 1 returns its bits */
+int32_t pvf_embed_chips_jitter(pvf_handle ctx, const uint8_t* chips, int32_t n, int32_t J, uint64_t seed, float* out /* n*128 */);
+
 /* ---- S5 clustering --------------------------------------------------------------------------------- */
 /* ref: clustering.py:100-112  -squareform(pdist(X,'euclidean')) reduced to the T x T matrix of block means;
  * X float64 [N][dim], rows grouped by track, row_start[T+1]; D float64 [T][T] (positive distances).

@@ -752,6 +752,112 @@ extern "C" int32_t pvf_embed_chips(pvf_handle h, const uint8_t* chips, int32_t n
     API_END
 }
 
+// ---- num_jitters: dlib's compute_face_descriptor(img, shape, num_jitters) (JITTER.md; jitter.hip) ----------------------------------
+// compute_face_descriptor(img, shape, num_jitters): the transforms of the J jitters, host only
+extern "C" int32_t pvf_jitter_plan(int32_t J, uint64_t seed, double* out)
+{
+    API_BEGIN
+    jitter_check_count("pvf_jitter_plan", J);
+    PVF_REQUIRE(out || J == 0, "pvf_jitter_plan: bad arguments");
+    jitter_plan_rows(J, seed, out);
+    API_END
+}
+
+static int32_t debug_jitter_chips(const char* who, pvf_handle h, const uint8_t* chips, int32_t n, int32_t J, uint64_t seed, uint8_t* out, bool via_transform)
+{
+    API_BEGIN
+    ENTER(c, h);
+    jitter_check_count(who, J);
+    PVF_REQUIRE(n >= 0 && J >= 1 && ((chips && (out || via_transform)) || n == 0), std::string(who) + ": bad arguments");
+    if (n == 0) return 0;
+    const size_t chip = (size_t)150 * 150 * 3;
+    c->s_trk0.ensure((size_t)n * chip);
+    HIP_CHECK(hipMemcpyAsync(c->s_trk0.p, chips, (size_t)n * chip, hipMemcpyHostToDevice, c->stream));
+    const int per = jitter_faces_per_round(J);
+    for (int i0 = 0; i0 < n; i0 += per) {
+        const int m = std::min(per, n - i0);
+        uint8_t* dj = jitter_scratch(c, m, J);
+        jitter_chips_dev(c, c->s_trk0.as<uint8_t>() + (size_t)i0 * chip, m, J, seed, dj, via_transform);
+        if (out) HIP_CHECK(hipMemcpyAsync(out + (size_t)i0 * J * chip, dj, (size_t)m * J * chip, hipMemcpyDeviceToHost, c->stream));
+        HIP_CHECK(hipStreamSynchronize(c->stream));
+    }
+    API_END
+}
+// compute_face_descriptor(img, shape, num_jitters): the jittered chips alone, [n][J][150][150][3]
+extern "C" int32_t pvf_debug_jitter_chips(pvf_handle h, const uint8_t* chips, int32_t n, int32_t J, uint64_t seed, uint8_t* out)
+{
+    return debug_jitter_chips("pvf_debug_jitter_chips", h, chips, n, J, seed, out, false);
+}
+// the same sampling by transform_k over n * J jobs, mirrored jitters left unmirrored: what tools/bench_jitter.py times jitter_k against
+extern "C" int32_t pvf_debug_jitter_chips_transform(pvf_handle h, const uint8_t* chips, int32_t n, int32_t J, uint64_t seed, uint8_t* out)
+{
+    return debug_jitter_chips("pvf_debug_jitter_chips_transform", h, chips, n, J, seed, out, true);
+}
+
+// what every descriptor entry with num_jitters checks before it does anything: 0 go on, -1 refused (pvf_last_error says why)
+static int32_t jitter_entry_check(const char* who, int32_t n, int32_t J, bool pointers)
+{
+    API_BEGIN
+    jitter_check_count(who, J);
+    PVF_REQUIRE(n >= 0 && (pointers || n == 0), std::string(who) + ": bad arguments");
+    API_END
+}
+
+// compute_face_descriptor(img, shape, num_jitters) for n faces: the fp32 mean of the descriptors of J jittered chips per face.
+// J <= 1: pvf_embed itself
+extern "C" int32_t pvf_embed_jitter(pvf_handle h, const pvf_handle* frames, const int32_t* pts, int32_t n, int32_t J, uint64_t seed, float* out)
+{
+    if (jitter_entry_check("pvf_embed_jitter", n, J, frames && pts && out)) return -1;
+    if (J <= 1) return pvf_embed(h, frames, pts, n, out);
+    API_BEGIN
+    ENTER(c, h);
+    const int CH = 4096; // faces per chip-extraction round, as in pvf_embed
+    for (int i0 = 0; i0 < n; i0 += CH) {
+        const int m = std::min(CH, n - i0);
+        uint8_t* d = make_face_chips(c, frames + i0, pts + (size_t)i0 * 136, m);
+        jitter_embed_dev(c, d, m, J, seed, out + (size_t)i0 * 128);
+    }
+    API_END
+}
+
+// get_landmarks, then compute_face_descriptor(img, shape, num_jitters), for n faces in one call.  J <= 1: pvf_landmarks_embed itself
+extern "C" int32_t pvf_landmarks_embed_jitter(pvf_handle h, const pvf_handle* frames, const pvf_rect_i32* boxes, int32_t n, int32_t J, uint64_t seed,
+                                              int32_t* pts, float* out)
+{
+    if (jitter_entry_check("pvf_landmarks_embed_jitter", n, J, frames && boxes && pts && out)) return -1;
+    if (J <= 1) return pvf_landmarks_embed(h, frames, boxes, n, pts, out);
+    API_BEGIN
+    ENTER(c, h);
+    if (n == 0) return 0;
+    {
+        std::vector<Frame> f(n);
+        for (int i = 0; i < n; ++i) f[i] = c->frame(frames[i]);
+        ert_run(c, f, boxes, n, pts);
+    }
+    const int CH = 4096;
+    for (int i0 = 0; i0 < n; i0 += CH) {
+        const int m = std::min(CH, n - i0);
+        uint8_t* d = make_face_chips(c, frames + i0, pts + (size_t)i0 * 136, m);
+        jitter_embed_dev(c, d, m, J, seed, out + (size_t)i0 * 128);
+    }
+    API_END
+}
+
+// compute_face_descriptor(img, shape, num_jitters) from ready-made chips (host buffer).  J <= 1: pvf_embed_chips itself
+extern "C" int32_t pvf_embed_chips_jitter(pvf_handle h, const uint8_t* chips, int32_t n, int32_t J, uint64_t seed, float* out)
+{
+    if (jitter_entry_check("pvf_embed_chips_jitter", n, J, chips && out)) return -1;
+    if (J <= 1) return pvf_embed_chips(h, chips, n, out);
+    API_BEGIN
+    ENTER(c, h);
+    if (n == 0) return 0;
+    const size_t bytes = (size_t)n * 150 * 150 * 3;
+    c->s_trk0.ensure(bytes);
+    HIP_CHECK(hipMemcpyAsync(c->s_trk0.p, chips, bytes, hipMemcpyHostToDevice, c->stream));
+    jitter_embed_dev(c, c->s_trk0.as<uint8_t>(), n, J, seed, out);
+    API_END
+}
+
 extern "C" int32_t pvf_debug_extract_chip(pvf_handle h, pvf_handle frame, const double rect[4], double cs, double sn, int32_t rows,
                                           int32_t cols, uint8_t* out)
 {

@@ -83,7 +83,6 @@ ChipJob chip_plan(const Frame& f, const ChipDetails& d)
 }
 
 struct DevPyrJob { const uint8_t* src; int stride_w, x0, y0; uint8_t* dst; int dh, dw; };
-struct DevXfJob { const uint8_t* src; int stride_w, x0, y0, sw, sh; double m[4], b[2]; };
 
 // pyramid_down<2>: separable 1-4-6-4-1 in integers, /256 truncating (exact: every partial sum is an integer below 2^16, any order
 // of the additions gives the same value).  A block of 256 threads makes a tile of 32 x 8 output pixels of one job: first the
@@ -152,6 +151,11 @@ __global__ void __launch_bounds__(256) transform_k(const DevXfJob* __restrict__ 
         const double v = (1 - tb) * ((1 - lr) * tl + lr * tr) + tb * ((1 - lr) * bl + lr * br);
         o[k] = (uint8_t)v;
     }
+}
+
+void transform_launch(Ctx* c, const DevXfJob* d_jobs, int n, int rows, int cols, uint8_t* d_out)
+{
+    hipLaunchKernelGGL(transform_k, dim3((cols + 63) / 64, rows, n), dim3(64), 0, c->stream, d_jobs, d_out, rows, cols);
 }
 
 // plain affine sampling straight from the frame (tracker scale space): jobs carry m,b; sub image = whole frame

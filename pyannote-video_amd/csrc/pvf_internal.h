@@ -216,6 +216,8 @@ struct ChipJob {
     bool empty;
 };
 struct ChipDetails { double l, t, r, b, cs, sn; int rows, cols; };
+// one job of transform_k (chip.hip): the sub image (x0, y0, sw, sh) of an image of row pitch stride_w, and the affine chip -> sub image
+struct DevXfJob { const uint8_t* src; int stride_w, x0, y0, sw, sh; double m[4], b[2]; };
 
 struct Ctx {
     int device = 0;
@@ -264,6 +266,9 @@ struct Ctx {
     // the embedder's convolutions on the f16 matrix cores with split operands (resnet.hip: conv_tile_k with ConvSplit; pvf_embedder_split)
     bool emb_split = true, emb_probe_done = false;
     DevBuf s_emb_flags, s_emb_redo;
+    // num_jitters (jitter.hip): the jittered chips of one round, [faces][J][150][150][3]; s_trk0 keeps the source chips
+    DevBuf s_jit;
+    bool jit_attr_set = false;
     int64_t emb_split_faces = 0, emb_reruns = 0;
     double emb_pipe_err = -1;                 // measured by embed_probe: worst |pipe - exact| / sum of magnitudes over K = 2304 accumulations
     int n_cu = 256;
@@ -389,6 +394,15 @@ void fhog_dims(int ih, int iw, int cell, int pad_r, int pad_c, int* fh, int* fw)
 ChipJob chip_plan(const Frame& f, const ChipDetails& d);
 void chip_extract_batch(Ctx* c, const std::vector<ChipJob>& jobs, uint8_t* d_out /* n*rows*cols*3, same dims */);
 void transform_batch(Ctx* c, const std::vector<ChipJob>& jobs, uint8_t* d_out);
+// transform_k over n jobs already on the device (no "chip" profiling scope of its own: the caller names the family)
+void transform_launch(Ctx* c, const DevXfJob* d_jobs, int n, int rows, int cols, uint8_t* d_out);
+// jittered chips (jitter.hip; JITTER.md)
+void jitter_check_count(const char* who, int J);
+void jitter_plan_rows(int J, uint64_t seed, double* out /* J * PVF_JITTER_ROW */);
+int jitter_faces_per_round(int J);
+uint8_t* jitter_scratch(Ctx* c, int faces, int J);
+void jitter_chips_dev(Ctx* c, const uint8_t* d_chips, int n, int J, uint64_t seed, uint8_t* d_out, bool via_transform);
+void jitter_embed_dev(Ctx* c, const uint8_t* d_chips, int n, int J, uint64_t seed, float* out);
 // landmarks (ert.hip)
 void ert_run(Ctx* c, const std::vector<Frame>& frames, const pvf_rect_i32* boxes, int n, int32_t* pts);
 // embedding (resnet.hip)

@@ -91,6 +91,13 @@ _SIGS = {
     "pvf_landmarks_embed": (C.c_int32, [H, P, P, C.c_int32, P, P]),
     "pvf_embed_chips": (C.c_int32, [H, P, C.c_int32, P]),
     "pvf_face_chips": (C.c_int32, [H, P, P, C.c_int32, P]),
+    # num_jitters (JITTER.md): compute_face_descriptor(img, shape, num_jitters)
+    "pvf_jitter_plan": (C.c_int32, [C.c_int32, C.c_uint64, P]),
+    "pvf_debug_jitter_chips": (C.c_int32, [H, P, C.c_int32, C.c_int32, C.c_uint64, P]),
+    "pvf_debug_jitter_chips_transform": (C.c_int32, [H, P, C.c_int32, C.c_int32, C.c_uint64, P]),
+    "pvf_embed_jitter": (C.c_int32, [H, P, P, C.c_int32, C.c_int32, C.c_uint64, P]),
+    "pvf_landmarks_embed_jitter": (C.c_int32, [H, P, P, C.c_int32, C.c_int32, C.c_uint64, P, P]),
+    "pvf_embed_chips_jitter": (C.c_int32, [H, P, C.c_int32, C.c_int32, C.c_uint64, P]),
     "pvf_pair_mean_dist": (C.c_int32, [H, P, C.c_int32, C.c_int32, P, C.c_int32, P]),
     "pvf_pair_mean_dist_metric": (C.c_int32, [H, P, C.c_int32, C.c_int32, P, C.c_int32, C.c_int32, P]),
     "pvf_pair_mean_dist_rows": (C.c_int32, [H, P, C.c_int32, C.c_int32, P, C.c_int32, C.c_int32, C.c_int32, P]),
@@ -282,6 +289,18 @@ def parse_rows(text):
         if b"too small" not in lib().pvf_last_error():
             break
     raise PvfError(lib().pvf_last_error().decode("utf-8", "replace"))
+
+
+JITTER_ROW = 17      # PVF_JITTER_ROW: l t r b cs sn flip m[4] b[2] bx0 by0 sw sh
+
+
+def jitter_plan(J, seed=0):
+    """the transforms of the J jitters of compute_face_descriptor(img, shape, num_jitters) (pvf_jitter_plan; JITTER.md): float64
+    [J, 17] rows of l t r b cs sn flip m[4] b[2] bx0 by0 sw sh.  Row j depends on (seed, j) alone."""
+    J = int(J)
+    out = np.zeros((max(J, 0), JITTER_ROW), np.float64)
+    check(lib().pvf_jitter_plan(J, int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(out)))
+    return out
 
 
 def munkres(cost):

@@ -151,14 +151,24 @@ def track(video, shot, output, detect_min_size=0.0, detect_every=0.0, track_min_
         return res
 
 
-def extract(video, landmark_model, embedding_model, tracking, landmark_output, embedding_output, ctx=None, batch=2048, ahead=96):
+def _jitter_kw(num_jitters, jitter_seed):
+    """what landmarks_embed gets beyond the faces: nothing without jitters (the call of before), else num_jitters and the seed"""
+    if int(num_jitters) < 0:
+        raise ValueError("--jitters must not be negative")
+    return {"num_jitters": int(num_jitters), "seed": int(jitter_seed)} if num_jitters else {}
+
+
+def extract(video, landmark_model, embedding_model, tracking, landmark_output, embedding_output, ctx=None, batch=2048, ahead=96,
+            num_jitters=0, jitter_seed=0):
     """Facial features (pyannote-face.py:271-314): landmarks.txt and embedding.txt for every face of the track file.  The faces
     are paired with frames by getFaceGenerator's rules (pipeline.faces_per_frame); a reader thread pushes the frames that carry faces
     through the pinned ingest ring (asynchronous uploads, at most `ahead` frames in flight) while this thread computes `batch` faces per
-    library call and writes the lines in the reference's order."""
+    library call and writes the lines in the reference's order.  num_jitters > 1: every descriptor is the mean over that many jittered
+    chips (dlib's compute_face_descriptor(img, shape, num_jitters); JITTER.md)."""
     import queue
     import threading
     from . import pipeline, runtime
+    jitter = _jitter_kw(num_jitters, jitter_seed)
     ctx = ctx or runtime.default_context()
     ctx.load_shape_predictor(landmark_model)
     ctx.load_embedder(embedding_model)
@@ -219,7 +229,7 @@ def extract(video, landmark_model, embedding_model, tracking, landmark_output, e
             def flush():
                 if not pend_b:
                     return
-                pts, emb = ctx.landmarks_embed(pend_f, pend_b)
+                pts, emb = ctx.landmarks_embed(pend_f, pend_b, **jitter)
                 wq.put(([k[0] for k in pend_k], [k[1] for k in pend_k], pts, emb))
                 for f in pend_own:
                     f.release()
@@ -349,12 +359,14 @@ def enroll_track(embeddings, track, name, gallery, append=False):
     return len(rows)
 
 
-def enroll(video, landmark_model, embedding_model, name, gallery, append=False, ctx=None, batch=16):
+def enroll(video, landmark_model, embedding_model, name, gallery, append=False, ctx=None, batch=16, num_jitters=0, jitter_seed=0):
     """Every frame of the video through detector -> landmarks -> embedder; the detection of largest area is enrolled (the first in
-    detector order on equal areas), frames without a face are skipped.  -> {"faces": enrolled, "skipped": frames without a face}"""
+    detector order on equal areas), frames without a face are skipped.  num_jitters > 1: every enrolled descriptor is the mean over that
+    many jittered chips (JITTER.md).  -> {"faces": enrolled, "skipped": frames without a face}"""
     import os
     from . import identification, runtime
     formats.check_gallery_name(name)
+    jitter = _jitter_kw(num_jitters, jitter_seed)
     if not append and os.path.exists(gallery):
         raise FileExistsError("%s exists: --append adds to it" % gallery)          # before any work
     ctx = ctx or runtime.default_context()
@@ -371,7 +383,7 @@ def enroll(video, landmark_model, embedding_model, name, gallery, append=False, 
                     area = [(b[2] - b[0] + 1) * (b[3] - b[1] + 1) for b in boxes]
                     keep_f.append(f); keep_b.append(boxes[area.index(max(area))])
             if keep_b:
-                rows.append(ctx.landmarks_embed(keep_f, keep_b)[1])
+                rows.append(ctx.landmarks_embed(keep_f, keep_b, **jitter)[1])
             return len(frames) - len(keep_b)
         finally:
             for f in frames:
@@ -531,6 +543,9 @@ def _parser():
     e = sub.add_parser("extract")
     for name in ("video", "tracking", "landmark_model", "embedding_model", "landmarks", "embeddings"):
         e.add_argument(name)
+    e.add_argument("--jitters", type=int, default=0, help="descriptors averaged over this many jittered face chips (dlib's num_jitters; "
+                    "0 or 1: the plain descriptor)")
+    e.add_argument("--jitter-seed", type=int, default=0, help="seed of the jitter transforms (they depend on the seed and the jitter's index alone)")
     pr = sub.add_parser("process", help="track + extract + cluster in one pass over the video")
     for name in ("video", "shot", "landmark_model", "embedding_model", "tracking", "landmarks", "embeddings"):
         pr.add_argument(name)
@@ -573,6 +588,9 @@ def _parser():
     for name in ("video", "landmark_model", "embedding_model", "name", "gallery"):
         en.add_argument(name)
     en.add_argument("--append", action="store_true", help="add to an existing gallery file (refused otherwise)")
+    en.add_argument("--jitters", type=int, default=0, help="descriptors averaged over this many jittered face chips (dlib's num_jitters; "
+                    "0 or 1: the plain descriptor)")
+    en.add_argument("--jitter-seed", type=int, default=0, help="seed of the jitter transforms (they depend on the seed and the jitter's index alone)")
     et = sub.add_parser("enroll-track", help="the rows of one track of an embedding file, under a name, into a gallery file")
     et.add_argument("embeddings"); et.add_argument("track", type=int); et.add_argument("name"); et.add_argument("gallery")
     et.add_argument("--append", action="store_true")
@@ -624,7 +642,8 @@ def main(argv=None):
     elif a.verb == "identify":
         identify(a.embeddings, a.gallery, a.output, threshold=a.threshold, metric=a.metric, labels=a.labels, unknown=a.unknown, scores=a.scores, ctx=ctx)
     elif a.verb == "enroll":
-        res = enroll(video(), a.landmark_model, a.embedding_model, a.name, a.gallery, append=a.append, ctx=ctx)
+        res = enroll(video(), a.landmark_model, a.embedding_model, a.name, a.gallery, append=a.append, ctx=ctx, num_jitters=a.jitters,
+                     jitter_seed=a.jitter_seed)
     elif a.verb == "enroll-track":
         enroll_track(a.embeddings, a.track, a.name, a.gallery, append=a.append)
     elif a.verb == "shot":
@@ -637,7 +656,8 @@ def main(argv=None):
                    label=a.label, matrix=a.matrix or getattr(v, "matrix", "601"),
                    full_range=(a.range == "full") if a.range is not None else bool(getattr(v, "full_range", False)), fps=a.fps, ctx=ctx)
     elif a.verb == "extract":
-        extract(video(), a.landmark_model, a.embedding_model, a.tracking, a.landmarks, a.embeddings, ctx=ctx)
+        extract(video(), a.landmark_model, a.embedding_model, a.tracking, a.landmarks, a.embeddings, ctx=ctx, num_jitters=a.jitters,
+                jitter_seed=a.jitter_seed)
     else:
         cluster(a.embeddings, a.labels, threshold=a.threshold, force=a.force, metric=a.metric, ctx=ctx, do_not_cooccur=a.do_not_cooccur)
     if a.metrics:

@@ -35,8 +35,8 @@ class Face(object):
     def get_landmarks(self, rgb, face):
         return self.shape_predictor_(rgb, face)
 
-    def get_embedding(self, rgb, landmarks):
-        return self.face_recognition_.compute_face_descriptor(rgb, landmarks)
+    def get_embedding(self, rgb, landmarks, num_jitters=0):
+        return self.face_recognition_.compute_face_descriptor(rgb, landmarks, num_jitters)
 
     def get_debug(self, image, face, landmarks):
         raise NotImplementedError("debug crops are visualisation (reference face.py:78-87 uses cv2 and an undefined self.size)")

@@ -691,17 +691,22 @@ class Context(object):
             check(self._l.pvf_landmarks(self._h, ptr(self._handles(frames)), ptr(r), n, ptr(pts)))
         return pts
 
-    def embed(self, frames, pts):
+    def embed(self, frames, pts, num_jitters=0, seed=0):
+        """descriptors of the faces; num_jitters > 1: dlib's compute_face_descriptor(img, shape, num_jitters) -- the fp32 mean over
+        that many jittered chips per face (JITTER.md), a function of the face, num_jitters and the seed"""
         pts = np.ascontiguousarray(pts, np.int32).reshape(-1, 68, 2)
         n = len(pts)
         out = np.zeros((n, 128), np.float32)
         if n == 0:
             return out
         with self._staging():
-            check(self._l.pvf_embed(self._h, ptr(self._handles(frames)), ptr(pts), n, ptr(out)))
+            if num_jitters:
+                check(self._l.pvf_embed_jitter(self._h, ptr(self._handles(frames)), ptr(pts), n, int(num_jitters), _seed64(seed), ptr(out)))
+            else:
+                check(self._l.pvf_embed(self._h, ptr(self._handles(frames)), ptr(pts), n, ptr(out)))
         return out
 
-    def landmarks_embed(self, frames, boxes):
+    def landmarks_embed(self, frames, boxes, num_jitters=0, seed=0):
         """landmarks() then embed() of the same faces in one library call: (int32 [n, 68, 2], float32 [n, 128])"""
         n = len(boxes)
         pts = np.zeros((n, 68, 2), np.int32)
@@ -710,7 +715,11 @@ class Context(object):
             return pts, out
         r = _rects(boxes, n)
         with self._staging():
-            check(self._l.pvf_landmarks_embed(self._h, ptr(self._handles(frames)), ptr(r), n, ptr(pts), ptr(out)))
+            if num_jitters:
+                check(self._l.pvf_landmarks_embed_jitter(self._h, ptr(self._handles(frames)), ptr(r), n, int(num_jitters), _seed64(seed),
+                                                         ptr(pts), ptr(out)))
+            else:
+                check(self._l.pvf_landmarks_embed(self._h, ptr(self._handles(frames)), ptr(r), n, ptr(pts), ptr(out)))
         return pts, out
 
     def face_chips(self, frames, pts):
@@ -721,10 +730,23 @@ class Context(object):
             check(self._l.pvf_face_chips(self._h, ptr(self._handles(frames)), ptr(pts), n, ptr(out)))
         return out
 
-    def embed_chips(self, chips):
+    def embed_chips(self, chips, num_jitters=0, seed=0):
         chips = np.ascontiguousarray(chips, np.uint8).reshape(-1, 150, 150, 3)
         out = np.zeros((len(chips), 128), np.float32)
-        check(self._l.pvf_embed_chips(self._h, ptr(chips), len(chips), ptr(out)))
+        if num_jitters:
+            check(self._l.pvf_embed_chips_jitter(self._h, ptr(chips), len(chips), int(num_jitters), _seed64(seed), ptr(out)))
+        else:
+            check(self._l.pvf_embed_chips(self._h, ptr(chips), len(chips), ptr(out)))
+        return out
+
+    def jitter_chips(self, chips, J, seed=0, via_transform=False, copy_out=True):
+        """the J jittered copies of every chip, uint8 [n, J, 150, 150, 3] (pvf_debug_jitter_chips; JITTER.md).  via_transform: the
+        measurement switch of tools/bench_jitter.py -- transform_k over n * J jobs, mirrored jitters left unmirrored; with copy_out off
+        the kernels run and nothing comes back (None)"""
+        chips = np.ascontiguousarray(chips, np.uint8).reshape(-1, 150, 150, 3)
+        out = np.zeros((len(chips), max(int(J), 0), 150, 150, 3), np.uint8) if copy_out or not via_transform else None
+        fn = self._l.pvf_debug_jitter_chips_transform if via_transform else self._l.pvf_debug_jitter_chips
+        check(fn(self._h, ptr(chips), len(chips), int(J), _seed64(seed), ptr(out)))
         return out
 
     def extract_chip(self, frame, rect, cs, sn, rows, cols):
@@ -1107,6 +1129,10 @@ class Context(object):
         ms, n = C.c_double(0), C.c_int64(0)
         check(self._l.pvf_prof_get(self._h, family.encode(), C.byref(ms), C.byref(n)))
         return ms.value, n.value
+
+
+def _seed64(seed):
+    return int(seed) & 0xFFFFFFFFFFFFFFFF
 
 
 _default = None

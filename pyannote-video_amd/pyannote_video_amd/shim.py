@@ -158,10 +158,11 @@ class face_recognition_model_v1(object):
         self._ctx.load_embedder(path)
 
     def compute_face_descriptor(self, rgb, shape, num_jitters=0):
-        if num_jitters not in (0, 1):
-            raise NotImplementedError("num_jitters > 1 is not on the reference's path (face.py:74-75 uses the default)")
+        """num_jitters > 1: the mean descriptor of that many jittered chips (JITTER.md), with this library's stream at seed 0"""
         pts = shape.as_array() if hasattr(shape, "as_array") else np.asarray([(p.x, p.y) for p in shape.parts()], np.int32)
-        return vector(self._ctx.embed([rgb], [pts])[0])
+        if num_jitters in (0, 1):
+            return vector(self._ctx.embed([rgb], [pts])[0])
+        return vector(self._ctx.embed([rgb], [pts], num_jitters=int(num_jitters), seed=0)[0])
 
 
 class correlation_tracker(object):
