@@ -374,6 +374,23 @@ def farneback_levels(h, w):
     return int(lib().pvo_farneback_levels(int(h), int(w)))
 
 
+def farneback_plan(h, w):
+    """the pyramid pvo_farneback walks for an h x w image: [(level height, level width, smoothing size, float32 taps)] for k = 0 .. levels
+    (level 0: the fixed 3 x 3 kernel, no taps)"""
+    lh, lw, sz = np.zeros(4, np.int32), np.zeros(4, np.int32), np.zeros(4, np.int32)
+    kern = np.zeros((4, 32), np.float32)
+    levels = int(lib().pvo_farneback_plan(int(h), int(w), _p(lh), _p(lw), _p(sz), _p(kern)))
+    return [(int(lh[k]), int(lw[k]), int(sz[k]), kern[k, :sz[k]].copy() if k else np.zeros(0, np.float32)) for k in range(levels + 1)]
+
+
+def shot_dfd_from_flow(prev, cur, flow):
+    """shot.py:89-99 on a given flow: mean |previous - current displaced by the flow|"""
+    prev = np.ascontiguousarray(prev, np.uint8); cur = np.ascontiguousarray(cur, np.uint8)
+    flow = np.ascontiguousarray(flow, np.float32)
+    assert prev.ndim == 2 and prev.shape == cur.shape and flow.shape == prev.shape + (2,)
+    return float(lib().pvo_shot_dfd_from_flow(_p(prev), _p(cur), prev.shape[0], prev.shape[1], _p(flow)))
+
+
 def farneback(prev, cur, tables=None):
     """cv2.calcOpticalFlowFarneback(prev, cur, None, 0.5, 3, 15, 3, 5, 1.1, 0) -> float32 [h, w, 2] (any size: up to three coarser levels)"""
     prev = np.ascontiguousarray(prev, np.uint8); cur = np.ascontiguousarray(cur, np.uint8)

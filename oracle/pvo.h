@@ -168,6 +168,7 @@ void pvo_shot_convert(const uint8_t* rgb, int ih, int iw, uint8_t* out /* [oh][o
 void pvo_shot_tables(float* t /* 22: g[6] xg[6] xxg[6] ig11 ig03 ig33 ig55 */);
 int pvo_farneback_small(const uint8_t* prev, const uint8_t* cur, int h, int w, const float* tables, float* flow /* [h][w][2] */);
 int pvo_farneback_levels(int h, int w);   /* coarser pyramid levels OpenCV uses for this size (0: an image side below 64 pixels) */
+int pvo_farneback_plan(int h, int w, int* lh /* [4] */, int* lw /* [4] */, int* smooth_sz /* [4] */, float* kern /* [4][32] */);   /* levels; per level size, smoothing size, taps */
 int pvo_farneback(const uint8_t* prev, const uint8_t* cur, int h, int w, const float* tables, float* flow /* [h][w][2] */);
 double pvo_shot_dfd_from_flow(const uint8_t* prev, const uint8_t* cur, int h, int w, const float* flow);
 double pvo_shot_dfd(const uint8_t* prev, const uint8_t* cur, int h, int w, const float* tables);

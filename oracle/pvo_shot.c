@@ -319,6 +319,32 @@ int pvo_farneback_levels(int h, int w)
     return k;
 }
 
+/* level k of the pyramid of an h x w image: its size, smoothing size and sigma (the arithmetic pvo_farneback works from) */
+static void level_plan(int h, int w, int k, int* lh, int* lw, int* smooth_sz, double* sigma)
+{
+    double scale = 1;
+    for (int i = 0; i < k; ++i) scale *= 0.5;
+    *sigma = (1. / scale - 1) * 0.5;
+    *smooth_sz = cv_round(*sigma * 5) | 1;
+    if (*smooth_sz < 3) *smooth_sz = 3;
+    *lw = cv_round(w * scale);
+    *lh = cv_round(h * scale);
+}
+
+/* what pvo_farneback does level by level, for the tests to read: returns the number of coarser levels; for k = 0 .. levels the level's
+ * size, its smoothing size and (k >= 1) its Gaussian taps in kern[k * 32 ...]; level 0 uses the fixed 3 x 3 kernel of blur3 */
+int pvo_farneback_plan(int h, int w, int* lh /* [4] */, int* lw /* [4] */, int* smooth_sz /* [4] */, float* kern /* [4][32] */)
+{
+    const int levels = pvo_farneback_levels(h, w);
+    memset(kern, 0, sizeof(float) * 4 * 32);
+    for (int k = 0; k <= levels; ++k) {
+        double sigma;
+        level_plan(h, w, k, lh + k, lw + k, smooth_sz + k, &sigma);
+        if (k > 0) gauss_kernel(smooth_sz[k], sigma, kern + k * 32);
+    }
+    return levels;
+}
+
 /* cv2.calcOpticalFlowFarneback(prev, cur, None, 0.5, 3, 15, 3, 5, 1.1, 0), any size: flow [h][w][2] */
 int pvo_farneback(const uint8_t* prev, const uint8_t* cur, int h, int w, const float* tables, float* flow)
 {
@@ -334,12 +360,9 @@ int pvo_farneback(const uint8_t* prev, const uint8_t* cur, int h, int w, const f
     float *fl = fa, *fl_prev = fb;
     int plh = 0, plw = 0;
     for (int k = levels; k >= 0; --k) {
-        double scale = 1;
-        for (int i = 0; i < k; ++i) scale *= 0.5;
-        const double sigma = (1. / scale - 1) * 0.5;
-        int smooth_sz = cv_round(sigma * 5) | 1;
-        if (smooth_sz < 3) smooth_sz = 3;
-        const int lw = cv_round(w * scale), lh = cv_round(h * scale);
+        double sigma;
+        int smooth_sz, lw, lh;
+        level_plan(h, w, k, &lh, &lw, &smooth_sz, &sigma);
         if (k == levels) memset(fl, 0, sizeof(float) * (size_t)lh * lw * 2);
         else {
             resize_linear_f(fl_prev, plh, plw, 2, fl, lh, lw);
