@@ -118,10 +118,24 @@ int32_t pvf_frame_resize(pvf_handle ctx, pvf_handle frame, int32_t out_w, int32_
  * reads.  Integer arithmetic throughout; DEMO.md states it.  flags: PVF_YUV_BT709 / PVF_YUV_FULL_RANGE.
  * A primitive is eight int32: rectangle outline (a, b, c, d) = (left, top, right, bottom), two pixels wide; line (a, b) - (c, d), one
  * pixel wide; text with (a, b) the bottom-left corner of the first glyph's 5 x 7 box, c and d the offset and length of its bytes in
- * the call's text pool, `scale` the side of a font pixel.  Coordinates are any int32.  colour = r | g << 8 | b << 16. */
+ * the call's text pool, `scale` the side of a font pixel.  Coordinates are any int32.  colour = r | g << 8 | b << 16.
+ * A redaction (REDACT.md) hides the box (a, b, c, d) = (left, top, right, bottom), corners inclusive, or the ellipse inscribed in it:
+ * `scale` is the side of a mosaic cell in output pixels, the top byte of `colour` carries PVF_REDACT_* flags.  A covered pixel shows the
+ * mean of its cell of the resized source picture (mosaic), a bilinear blend of the neighbouring cells' means (smooth) or `colour`
+ * (fill).  `reserved` is the library's: it is overwritten in the device copy of the list, whatever the caller puts there. */
 #define PVF_PRIM_RECT 0
 #define PVF_PRIM_LINE 1
 #define PVF_PRIM_TEXT 2
+#define PVF_PRIM_REDACT 3
+#define PVF_REDACT_ELLIPSE 1            /* flags bit 0: the ellipse inscribed in the box (otherwise the box) */
+#define PVF_REDACT_MOSAIC 0             /* flags bits 1-2: the mode */
+#define PVF_REDACT_SMOOTH 2
+#define PVF_REDACT_FILL 4
+#define PVF_REDACT_MAX_SIDE 16384       /* width and height of a redaction's box */
+#define PVF_REDACT_MAX_COORD (1 << 20)  /* |coordinate| of a redaction */
+#define PVF_REDACT_MAX_CELL 2048        /* side of a cell: a cell's sum stays below 2^31 */
+#define PVF_REDACT_MAX_CELLS 4096       /* cells per redaction */
+#define PVF_REDACT_MAX_TABLE (1 << 22)  /* cells of all the redactions of one call */
 #define PVF_RENDER_MAX_PRIMS 4096       /* primitives per frame */
 #define PVF_RENDER_MAX_RUN 64           /* bytes per text primitive */
 #define PVF_RENDER_MAX_TEXT (1 << 20)   /* text bytes per call */
@@ -149,6 +163,11 @@ int32_t pvf_egress_release(pvf_handle ctx, pvf_handle ring, int32_t slot);
 /* the drawn picture BEFORE colour conversion, uint8 RGB [out_h][out_w][3] to host memory: tells resize, drawing and conversion apart */
 int32_t pvf_debug_render_rgb(pvf_handle ctx, pvf_handle frame, int32_t out_w, int32_t out_h, const pvf_prim* prims, int32_t n_prims,
                              const uint8_t* text, int64_t text_bytes, uint8_t* rgb);
+/* the cell means the list's redactions are drawn from, BEFORE composition: the tables of the list's mosaic and smooth redactions,
+ * concatenated in list order, a table's cells row-major, 3 bytes (R, G, B) a cell, to host memory.  An inverted box and a fill have no
+ * table; a cell wholly outside the frame reads 0, 0, 0.  `capacity` is the size of `means` in bytes: refused when the tables need more. */
+int32_t pvf_debug_redact_means(pvf_handle ctx, pvf_handle frame, int32_t out_w, int32_t out_h, const pvf_prim* prims, int32_t n_prims,
+                               uint8_t* means, int64_t capacity);
 
 /* ---- S1 detector ---------------------------------------------------------------------------------- */
 /* ref: face.py:64-67  for face in self.face_detector_(rgb, 1)  -> dlib.rectangle list, NMS order.

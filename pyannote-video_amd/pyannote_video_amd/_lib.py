@@ -64,6 +64,7 @@ _SIGS = {
     "pvf_egress_wait": (C.c_int32, [H, H, C.c_int32, P]),
     "pvf_egress_release": (C.c_int32, [H, H, C.c_int32]),
     "pvf_debug_render_rgb": (C.c_int32, [H, H, C.c_int32, C.c_int32, P, C.c_int32, P, C.c_int64, P]),
+    "pvf_debug_redact_means": (C.c_int32, [H, H, C.c_int32, C.c_int32, P, C.c_int32, P, C.c_int64]),
     "pvf_detect": (C.c_int32, [H, H, C.c_int32, C.c_double, P, P, C.c_int32, P]),
     "pvf_detect_batch": (C.c_int32, [H, P, C.c_int32, C.c_int32, C.c_double, P, P, P, C.c_int32]),
     "pvf_detect_many": (C.c_int32, [H, P, C.c_int32, C.c_int32, C.c_int32, C.c_double, P, P, P, C.c_int32]),

@@ -10,6 +10,8 @@
     python -m pyannote_video_amd enroll-track [--append] <embeddings> <track> <name> <gallery>
     python -m pyannote_video_amd identify [--threshold 0.6] [--metric euclidean|cosine] [--labels PATH] [--unknown NAME] [--scores PATH] <embeddings> <gallery> <output>
     python -m pyannote_video_amd demo    [--height 400] [--from 0] [--until T] [--shift 0] [--landmark PATH] [--label PATH] <video> <tracking> <output>
+    python -m pyannote_video_amd redact  [--height 0] [--from 0] [--until T] [--shift 0] [--label PATH] [--only A,B | --keep A,B] [--pad 25] [--cells 8]
+                                         [--shape ellipse|box] [--mode mosaic|smooth|fill] [--colour r,g,b] [--draw] <video> <tracking> <output>
 
 `track` and `extract` take the reference's arguments and options and write byte-compatible files (track.txt, landmarks.txt,
 embedding.txt: formats.py).  `cluster` is the verb BASELINE.json's north_star names; the reference offers clustering through the API
@@ -20,6 +22,8 @@ only (face/clustering.py:130-134).  It writes `identifier label` lines, the file
 on it, as a YUV4MPEG2 stream: to a `.y4m` path, or to stdout for `-` (`... demo film.y4m track.txt - | ffmpeg -i - out.mp4`).  Resize,
 drawing and RGB -> YUV 4:2:0 run in one kernel on the GPU (DEMO.md states every pixel; the font is the project's own, not OpenCV's
 Hershey).  Audio is not carried: the reference hands the source's audio track to moviepy, a Y4M stream has none.
+`redact` (no reference verb; REDACT.md) writes the same stream with the faces of the chosen tracks pixelated, blended or filled: a cell-mean
+reduction on the GPU in front of the same kernel.  It hides what the tracking file holds; a face the detector never found stays visible.
 
 <video>: no codec is linked (reference video.py:345-406 runs ffmpeg); the verbs read what a decoder writes --
   * a YUV4MPEG2 file (`.y4m`, or any file that starts with `YUV4MPEG2`): 8-bit 4:2:0 / 4:2:2 / 4:4:4, memory mapped, frame rate from
@@ -428,8 +432,6 @@ def demo(video, tracking, output, height=400, t_from=0.0, t_until=None, shift=0.
     shows through the pinned ingest ring (RGB or YUV, as `track` does), this thread submits one render per output frame to the egress
     ring, a writer thread waits for the slots and writes them: rendering frame k + 1 overlaps the copy of frame k and the write of
     frame k - 1.  Audio is not carried.  Returns {"frames": output frames, "width", "height"}."""
-    import queue
-    import threading
     from . import render, runtime
     ctx = ctx or runtime.default_context()
     vw, vh = video.size
@@ -439,12 +441,21 @@ def demo(video, tracking, output, height=400, t_from=0.0, t_until=None, shift=0.
     marks = formats.read_landmarks(landmark) if isinstance(landmark, str) else landmark
     rows = formats.read_tracks(tracking) if isinstance(tracking, str) else tracking
     plan = render.build_plan(rows, rate, len(video), width, height, marks, labels, t_from, t_until, shift)
+    return _render_plan(video, plan, output, width, height, matrix, full_range, fps if fps is not None else rate, ctx, ring_depth)
+
+
+def _render_plan(video, plan, output, width, height, matrix, full_range, fps, ctx, ring_depth):
+    """What `demo` and `redact` share: the frames a plan of (source index, t, primitives) shows go reader thread -> pinned ingest ring ->
+    one render per output frame into the egress ring (this thread) -> writer thread -> YUV4MPEG2."""
+    import queue
+    import threading
+    from . import render, runtime
     by_index = {}
     for k, (i, _, _) in enumerate(plan):
         by_index.setdefault(i, []).append(k)
     last_wanted = max(by_index) if by_index else -1
     ring = ctx.egress_ring(width, height, matrix, full_range, depth=ring_depth)
-    writer = render.Y4mWriter(output, width, height, render.rate_tag(video, fps if fps is not None else rate), full_range)
+    writer = render.Y4mWriter(output, width, height, render.rate_tag(video, fps), full_range)
     q = queue.Queue(maxsize=max(2, ring_depth))
     wq = queue.Queue()
     free = threading.Semaphore(ring_depth)             # slots the writer has given back
@@ -521,6 +532,41 @@ def demo(video, tracking, output, height=400, t_from=0.0, t_until=None, shift=0.
     if state["error"] is not None:
         raise state["error"]
     return {"frames": writer.frames, "width": width, "height": height}
+
+
+def redact(video, tracking, output, height=0, t_from=0.0, t_until=None, shift=0.0, label=None, only=None, keep=None, pad=25, cells=8,
+           shape="ellipse", mode="mosaic", colour=(0, 0, 0), draw=False, matrix="601", full_range=False, fps=None, ctx=None, ring_depth=16):
+    """The video with the faces of the chosen tracks hidden (REDACT.md), as YUV4MPEG2 to a path or to stdout (`-`): pixelated
+    (`mosaic`), pixelated and blended (`smooth`) or filled with `colour`.  height 0 keeps the source size.  only / keep: label names
+    (render.build_redaction_plan's selection); draw: `demo`'s primitives on top of the redactions.  It hides what the tracking file
+    holds: a face the detector never found stays visible.  Returns {"frames", "width", "height", "redactions"}."""
+    from . import render, runtime
+    ctx = ctx or runtime.default_context()
+    vw, vh = video.size
+    width, height = (int(vw), int(vh)) if not height else render.demo_size(vw, vh, height)
+    rate = float(video.frame_rate)
+    labels = render.read_labels(label) if isinstance(label, str) else label
+    rows = formats.read_tracks(tracking) if isinstance(tracking, str) else tracking
+    plan = render.build_redaction_plan(rows, rate, len(video), width, height, labels, only, keep, pad, cells, shape, mode, colour,
+                                       t_from, t_until, shift)
+    count = sum(len(prims) for _, _, prims in plan)
+    if draw:
+        drawn = render.build_plan(rows, rate, len(video), width, height, None, labels, t_from, t_until, shift)
+        plan = [(i, t, prims + more) for (i, t, prims), (_, _, more) in zip(plan, drawn)]
+    res = _render_plan(video, plan, output, width, height, matrix, full_range, fps if fps is not None else rate, ctx, ring_depth)
+    res["redactions"] = count
+    return res
+
+
+def _names(text):
+    return set(n for n in text.split(",") if n)
+
+
+def _colour(text):
+    c = tuple(int(v) for v in text.split(","))
+    if len(c) != 3 or not all(0 <= v <= 255 for v in c):
+        raise argparse.ArgumentTypeError("a colour is r,g,b with each 0 .. 255")
+    return c
 
 
 def _parser():
@@ -602,6 +648,23 @@ def _parser():
     d.add_argument("--shift", type=float, default=0.0, help="shift the tracks by this many seconds")
     d.add_argument("--landmark", default=None, help="landmarks.txt of `extract`: draws the nose line")
     d.add_argument("--label", default=None, help="`identifier label` lines, what `cluster` writes")
+    rd = sub.add_parser("redact", help="the video with the faces of chosen tracks pixelated or filled, as YUV4MPEG2")
+    rd.add_argument("video"); rd.add_argument("tracking"); rd.add_argument("output", help="a .y4m path, or - for stdout")
+    rd.add_argument("--height", type=int, default=0, help="height of the output frames (0, the default: the source size)")
+    rd.add_argument("--from", dest="t_from", type=float, default=0.0, help="start, seconds")
+    rd.add_argument("--until", dest="t_until", type=float, default=None, help="end, seconds (default: the video's duration)")
+    rd.add_argument("--shift", type=float, default=0.0, help="shift the tracks by this many seconds")
+    rd.add_argument("--label", default=None, help="`identifier name` lines, what `cluster` and `identify` write")
+    which = rd.add_mutually_exclusive_group()
+    which.add_argument("--only", type=_names, default=None, metavar="A,B", help="redact only the tracks with these labels (needs --label)")
+    which.add_argument("--keep", type=_names, default=None, metavar="A,B", help="redact every track but those with these labels; a track "
+                       "without a label is redacted (needs --label)")
+    rd.add_argument("--pad", type=int, default=25, help="per cent of the box's width / height added on each side")
+    rd.add_argument("--cells", type=int, default=8, help="mosaic cells along the longer side of the padded box")
+    rd.add_argument("--shape", choices=("ellipse", "box"), default="ellipse")
+    rd.add_argument("--mode", choices=("mosaic", "smooth", "fill"), default="mosaic")
+    rd.add_argument("--colour", type=_colour, default=(0, 0, 0), metavar="r,g,b", help="the fill colour")
+    rd.add_argument("--draw", action="store_true", help="draw what `demo` draws on top of the redactions")
     return ap
 
 
@@ -655,6 +718,16 @@ def main(argv=None):
         res = demo(v, a.tracking, a.output, height=a.height, t_from=a.t_from, t_until=a.t_until, shift=a.shift, landmark=a.landmark,
                    label=a.label, matrix=a.matrix or getattr(v, "matrix", "601"),
                    full_range=(a.range == "full") if a.range is not None else bool(getattr(v, "full_range", False)), fps=a.fps, ctx=ctx)
+    elif a.verb == "redact":
+        if (a.only is not None or a.keep is not None) and a.label is None:
+            ap.error("--only / --keep select by label: they need --label")
+        if a.cells < 1 or a.pad < 0:
+            ap.error("--cells is at least 1 and --pad at least 0")
+        v = video()
+        res = redact(v, a.tracking, a.output, height=a.height, t_from=a.t_from, t_until=a.t_until, shift=a.shift, label=a.label, only=a.only,
+                     keep=a.keep, pad=a.pad, cells=a.cells, shape=a.shape, mode=a.mode, colour=a.colour, draw=a.draw,
+                     matrix=a.matrix or getattr(v, "matrix", "601"),
+                     full_range=(a.range == "full") if a.range is not None else bool(getattr(v, "full_range", False)), fps=a.fps, ctx=ctx)
     elif a.verb == "extract":
         extract(video(), a.landmark_model, a.embedding_model, a.tracking, a.landmarks, a.embeddings, ctx=ctx, num_jitters=a.jitters,
                 jitter_seed=a.jitter_seed)

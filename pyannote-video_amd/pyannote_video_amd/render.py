@@ -1,11 +1,13 @@
 """The host side of the `demo` verb (reference scripts/pyannote-face.py:317-413): what is drawn on which output frame, and the
 YUV4MPEG2 stream the annotated frames leave in.  The pixels are made on the GPU (csrc/render.hip); DEMO.md states the semantics,
-tests/demo_ref.py restates them in numpy.  Nothing in this module needs a GPU.
+tests/demo_ref.py restates them in numpy.  Nothing in this module needs a GPU.  The `redact` verb (REDACT.md, tests/redact_ref.py)
+plans with build_redaction_plan() and leaves through the same kernel and stream.
 
     FONT, glyph()        the project's 5 x 7 bitmap font, ASCII 32 .. 126
     PALETTE              26 track colours (golden-angle hue steps through an integer HSV -> RGB)
     YUV_TABLES           the 16.16 RGB -> YUV coefficients per (matrix, full_range)
     build_plan()         track rows, landmark rows, labels, times and shift -> per-frame primitive lists
+    build_redaction_plan()   track rows, labels and a selection -> per-frame lists of redaction primitives
     pack_primitives()    those lists -> the CSR arrays pvf_render_batch / pvf_egress_submit take
     Y4mWriter            `YUV4MPEG2 W H F C420` to a path or to stdout
 """
@@ -13,7 +15,15 @@ import sys
 from fractions import Fraction
 import numpy as np
 
-PRIM_RECT, PRIM_LINE, PRIM_TEXT = 0, 1, 2
+PRIM_RECT, PRIM_LINE, PRIM_TEXT, PRIM_REDACT = 0, 1, 2, 3
+REDACT_ELLIPSE = 1                                    # flags bit 0 (PVF_REDACT_ELLIPSE): the ellipse inscribed in the box
+REDACT_MOSAIC, REDACT_SMOOTH, REDACT_FILL = 0, 2, 4   # flags bits 1-2 (PVF_REDACT_*): the mode
+REDACT_MODES = {"mosaic": REDACT_MOSAIC, "smooth": REDACT_SMOOTH, "fill": REDACT_FILL}
+REDACT_MAX_SIDE = 16384   # PVF_REDACT_MAX_SIDE
+REDACT_MAX_COORD = 1 << 20
+REDACT_MAX_CELL = 2048
+REDACT_MAX_CELLS = 4096   # per redaction
+REDACT_MAX_TABLE = 1 << 22   # cells of all the redactions of one call
 MAX_PRIMS = 4096          # per frame (PVF_RENDER_MAX_PRIMS)
 MAX_TEXT_RUN = 64         # bytes per text primitive (PVF_RENDER_MAX_RUN): longer labels are cut
 MAX_TEXT_BYTES = 1 << 20  # per call (PVF_RENDER_MAX_TEXT)
@@ -143,13 +153,9 @@ def landmark_groups(rows, width, height):
     return groups[:-1]
 
 
-def build_plan(track_rows, frame_rate, n_frames, width, height, landmark_rows=None, labels=None, t_from=0.0, t_until=None, shift=0.0):
-    """[(source frame index, t, [primitive])] for every output frame: frame k has t = t_from + k / frame_rate while t < t_until (default:
-    the video's duration, n_frames / frame_rate) and shows source frame int(frame_rate * t + 1e-5) (video.py:466-486); the output ends
-    where the video does.  Faces are what getFaceGenerator yields for t - shift (pipeline.faces_per_frame), landmarks what
-    getLandmarkGenerator yields, paired with the faces BY IDENTIFIER (DEMO.md, "Departures").  Primitives:
-        (PRIM_RECT, l, t, r, b, colour)   (PRIM_LINE, x1, y1, x2, y2, colour)   (PRIM_TEXT, x, y, colour, scale, bytes)"""
-    from .pipeline import faces_per_frame
+def plan_times(frame_rate, n_frames, t_from=0.0, t_until=None):
+    """(times, source frame indices) of the output frames: frame k has t = t_from + k / frame_rate while t < t_until (default: the
+    video's duration) and shows source frame int(frame_rate * t + 1e-5) (video.py:466-486); the output ends where the video does"""
     frame_rate = float(frame_rate)
     if t_until is None:
         t_until = n_frames / frame_rate
@@ -163,6 +169,17 @@ def build_plan(track_rows, frame_rate, n_frames, width, height, landmark_rows=No
         times.append(t)
         index.append(i)
         k += 1
+    return times, index
+
+
+def build_plan(track_rows, frame_rate, n_frames, width, height, landmark_rows=None, labels=None, t_from=0.0, t_until=None, shift=0.0):
+    """[(source frame index, t, [primitive])] for every output frame: frame k has t = t_from + k / frame_rate while t < t_until (default:
+    the video's duration, n_frames / frame_rate) and shows source frame int(frame_rate * t + 1e-5) (video.py:466-486); the output ends
+    where the video does.  Faces are what getFaceGenerator yields for t - shift (pipeline.faces_per_frame), landmarks what
+    getLandmarkGenerator yields, paired with the faces BY IDENTIFIER (DEMO.md, "Departures").  Primitives:
+        (PRIM_RECT, l, t, r, b, colour)   (PRIM_LINE, x1, y1, x2, y2, colour)   (PRIM_TEXT, x, y, colour, scale, bytes)"""
+    from .pipeline import faces_per_frame
+    times, index = plan_times(frame_rate, n_frames, t_from, t_until)
     sent = [t - shift for t in times]
     faces = {k: g for k, _, g in faces_per_frame(track_rows, sent, width, height)}
     marks = _paced(landmark_groups(landmark_rows, width, height), sent) if landmark_rows is not None else None
@@ -189,10 +206,99 @@ def build_plan(track_rows, frame_rate, n_frames, width, height, landmark_rows=No
     return plan
 
 
+def redaction_box(box, pad=25):
+    """the box a face's redaction covers: ((r - l) * pad + 50) // 100 more on the left and on the right, `pad` an integer per cent, and
+    the same rule with b - t above and below (REDACT.md "The verb")"""
+    l, t, r, b = (int(v) for v in box)
+    dx, dy = ((r - l) * pad + 50) // 100, ((b - t) * pad + 50) // 100
+    return l - dx, t - dy, r + dx, b + dy
+
+
+def redaction_cell(box, cells=8):
+    """the cell side for `cells` cells along the longer side of the (padded) box: max(1, ceil(max(W, H) / cells)), at most
+    REDACT_MAX_CELL, raised as far as REDACT_MAX_CELLS asks"""
+    W, H = max(1, box[2] - box[0] + 1), max(1, box[3] - box[1] + 1)
+    cell = min(REDACT_MAX_CELL, max(1, -(-max(W, H) // int(cells))))
+    while (-(-W // cell)) * (-(-H // cell)) > REDACT_MAX_CELLS:
+        cell += 1
+    return cell
+
+
+def redaction_cells(p):
+    """cells in the table of a (PRIM_REDACT, ...) primitive: 0 for an inverted box and for a fill"""
+    W, H = p[3] - p[1] + 1, p[4] - p[2] + 1
+    if W < 1 or H < 1 or (p[7] & 6) == REDACT_FILL:
+        return 0
+    return (-(-W // p[6])) * (-(-H // p[6]))
+
+
+def _check_redaction(p):
+    """the limits of REDACT.md, as the library checks them (render_launch)"""
+    _, l, t, r, b, colour, cell, flags = p
+    for v in (l, t, r, b):
+        if not -REDACT_MAX_COORD <= int(v) <= REDACT_MAX_COORD:
+            raise ValueError("redaction coordinate %r beyond +-%d" % (v, REDACT_MAX_COORD))
+    if int(flags) & ~7 or (int(flags) & 6) == 6:
+        raise ValueError("unknown redaction flags %r" % (flags,))
+    if not 1 <= int(cell) <= REDACT_MAX_CELL:
+        raise ValueError("redaction cell %r outside 1 .. %d" % (cell, REDACT_MAX_CELL))
+    W, H = int(r) - int(l) + 1, int(b) - int(t) + 1
+    if W < 1 or H < 1:
+        return
+    if W > REDACT_MAX_SIDE or H > REDACT_MAX_SIDE:
+        raise ValueError("a redaction of %d x %d pixels (a side is at most %d)" % (W, H, REDACT_MAX_SIDE))
+    n = (-(-W // int(cell))) * (-(-H // int(cell)))
+    if n > REDACT_MAX_CELLS:
+        raise ValueError("a redaction of %d cells (at most %d)" % (n, REDACT_MAX_CELLS))
+
+
+def build_redaction_plan(track_rows, frame_rate, n_frames, width, height, labels=None, only=None, keep=None, pad=25, cells=8,
+                         shape="ellipse", mode="mosaic", colour=(0, 0, 0), t_from=0.0, t_until=None, shift=0.0):
+    """[(source frame index, t, [primitive])] as build_plan gives them, the primitives being the redactions of the chosen tracks:
+        (PRIM_REDACT, l, t, r, b, colour, cell, flags)
+    Faces are pipeline.faces_per_frame(..., drop_last=False): the LAST time's faces are there too (the reference's generator never emits
+    them, and `demo` follows it; here that would leave a face visible).  Neither `only` nor `keep`: every track; only={names}: the tracks
+    whose label is in the set; keep={names}: every track whose label is NOT in the set, tracks without a label included (the safe side).
+    Both, or either without `labels`, is a ValueError.  The box is padded by redaction_box, the cell chosen by redaction_cell."""
+    from .pipeline import faces_per_frame
+    if only is not None and keep is not None:
+        raise ValueError("only and keep exclude each other")
+    if (only is not None or keep is not None) and labels is None:
+        raise ValueError("only / keep select by label: they need labels")
+    if shape not in ("ellipse", "box"):
+        raise ValueError("shape is 'ellipse' or 'box', not %r" % (shape,))
+    if mode not in REDACT_MODES:
+        raise ValueError("mode is one of %s, not %r" % (", ".join(sorted(REDACT_MODES)), mode))
+    flags = REDACT_MODES[mode] | (REDACT_ELLIPSE if shape == "ellipse" else 0)
+    colour = tuple(int(v) for v in colour)
+    only = None if only is None else set(only)
+    keep = None if keep is None else set(keep)
+
+    def chosen(ident):
+        if only is not None:
+            return ident in labels and labels[ident] in only
+        if keep is not None:
+            return not (ident in labels and labels[ident] in keep)
+        return True
+    times, index = plan_times(frame_rate, n_frames, t_from, t_until)
+    faces = {k: g for k, _, g in faces_per_frame(track_rows, [t - shift for t in times], width, height, drop_last=False)}
+    plan = []
+    for k, t in enumerate(times):
+        prims = []
+        for ident, box in faces.get(k, ()):
+            if chosen(ident):
+                padded = redaction_box(box, pad)
+                prims.append((PRIM_REDACT,) + padded + (colour, redaction_cell(padded, cells), flags))
+        plan.append((index[k], t, prims))
+    return plan
+
+
 def pack_primitives(lists):
     """per-frame primitive lists -> (start int32 [n + 1], prims int32 [N, 8], text uint8 [T]): the CSR form of the C ABI.  A row is
-    (type, a, b, c, d, colour = r | g << 8 | b << 16, scale, 0); text: a, b = x, y; c, d = offset into the pool and length."""
+    (type, a, b, c, d, colour = r | g << 8 | b << 16, scale, 0); text: a, b = x, y; c, d = offset into the pool and length; a
+    redaction (PRIM_REDACT, l, t, r, b, colour, cell, flags): colour | flags << 24, scale = cell."""
     start, rows, pool = [0], [], bytearray()
+    table = 0
     for prims in lists:
         if len(prims) > MAX_PRIMS:
             raise ValueError("%d primitives on one frame (at most %d)" % (len(prims), MAX_PRIMS))
@@ -203,6 +309,12 @@ def pack_primitives(lists):
                     raise ValueError("a text run of %d bytes (at most %d)" % (len(b), MAX_TEXT_RUN))
                 a = (x, y, len(pool), len(b))
                 pool += b
+            elif p[0] == PRIM_REDACT:
+                _check_redaction(p)
+                table += redaction_cells(p)
+                if table > REDACT_MAX_TABLE:
+                    raise ValueError("more than %d redaction cells in one call" % REDACT_MAX_TABLE)
+                colour, scale, a = (p[5][0], p[5][1], p[5][2] | int(p[7]) << 8), int(p[6]), p[1:5]      # the flags land in the top byte
             else:
                 colour, scale, a = p[5], 0, p[1:5]
             for v in a:

@@ -397,7 +397,7 @@ class Context(object):
 
     def render(self, frames, prims, width, height, matrix="601", full_range=False, out_ptr=None):
         """the `demo` picture of n resident frames of one size (pvf_render_batch): resized to (width, height), frame i drawn over with
-        prims[i] (render.py primitive lists; None: nothing is drawn), converted to planar YUV 4:2:0.  Returns uint8 [n, frame bytes]
+        prims[i] (render.py primitive lists, redactions included; None: nothing is drawn), converted to planar YUV 4:2:0.  Returns uint8 [n, frame bytes]
         (Y, U, V tight per frame); with out_ptr, a device address that holds as much, the planes stay in HBM and nothing is returned.
         prims may also be the packed (start, prims, text) arrays of render.pack_primitives."""
         from . import render as _render
@@ -426,6 +426,16 @@ class Context(object):
         out = np.empty((int(height), int(width), 3), np.uint8)
         check(self._l.pvf_debug_render_rgb(self._h, self.stage(frame).handle, int(width), int(height), ptr(p), len(p), ptr(text), len(text),
                                            ptr(out)))
+        return out
+
+    def redact_means(self, frame, prims, width, height):
+        """the cell means the list's redactions are drawn from, uint8 [cells, 3]: the tables of its mosaic and smooth redactions in list
+        order, a table's cells row-major (pvf_debug_redact_means).  Tells the reduction from the composition."""
+        from . import render as _render
+        _, p, _ = _render.pack_primitives([[q for q in prims if q[0] == _render.PRIM_REDACT]])
+        n = sum(_render.redaction_cells(q) for q in prims if q[0] == _render.PRIM_REDACT)
+        out = np.empty((n, 3), np.uint8)
+        check(self._l.pvf_debug_redact_means(self._h, self.stage(frame).handle, int(width), int(height), ptr(p), len(p), ptr(out), out.nbytes))
         return out
 
     def frame_from_yuv_device(self, y_ptr, y_pitch, u_ptr, v_ptr, c_pitch, height, width, layout="420", matrix="601", full_range=False,
