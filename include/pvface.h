@@ -141,6 +141,11 @@ int32_t pvf_frame_resize(pvf_handle ctx, pvf_handle frame, int32_t out_w, int32_
 #define PVF_RENDER_MAX_TEXT (1 << 20)   /* text bytes per call */
 #define PVF_RENDER_MAX_SCALE 64
 #define PVF_RENDER_MAX_BATCH 1024       /* frames per pvf_render_batch call */
+#define PVF_SHEET_MIN_TILE 48            /* side S of a contact sheet's tiles (FACES.md) */
+#define PVF_SHEET_MAX_TILE 600           /* (four weights x 255 + 2 S^2 stays below 2^31) */
+#define PVF_SHEET_MAX_SIDE 16384         /* width and height of a sheet */
+#define PVF_SHEET_MAX_PIXELS (1 << 26)   /* width x height of a sheet */
+#define PVF_SHEET_MAX_TILES 65536        /* tiles of a sheet, and chips of one quality call */
 typedef struct { int32_t type, a, b, c, d; uint32_t colour; int32_t scale, reserved; } pvf_prim;
 /* n resident frames of one size into `out` (n planar frames, tight; host memory, or device memory with out_on_device = 1); frame i
  * draws prims[start[i] .. start[i + 1]) (start == NULL: nothing is drawn).  Complete when the call returns.  Refused with an error:
@@ -270,6 +275,30 @@ int32_t pvf_landmarks_embed(pvf_handle ctx, const pvf_handle* frames, const pvf_
 int32_t pvf_embed_chips(pvf_handle ctx, const uint8_t* chips, int32_t n, float* out /* n*128 */);
 /* the aligned chips alone (get_face_chip_details + extract_image_chips), for testing K6 in isolation */
 int32_t pvf_face_chips(pvf_handle ctx, const pvf_handle* frames, const int32_t* pts, int32_t n, uint8_t* chips /* n*150*150*3 */);
+
+/* ---- faces: the quality of face chips and the contact sheet (FACES.md; no reference call) -------- */
+/* Five int64 per chip (uint8 [150][150][3], what the face chip call returns): S1 = sum of L, S2 = sum of L^2 over
+ * the 148 x 148 interior pixels, L the 4-neighbour Laplacian of the luma Y = (77 R + 150 G + 29 B + 128) >> 8; SY = sum of Y,
+ * ND = #{Y <= 16}, NB = #{Y >= 239} over all 22 500 pixels.  Integer sums: the result does not depend on the shape of the reduction.
+ * The chips come from host memory and go through the device in rounds of 4096.  n = 0 does nothing; refused: n < 0 or beyond
+ * PVF_SHEET_MAX_TILES, null pointers with n > 0. */
+int32_t pvf_chip_quality(pvf_handle ctx, const uint8_t* chips, int32_t n, int64_t* out /* n*5 */);
+/* the same five values for the faces given by frame and 68 landmarks: the chips are made on the device as the embedder's are and
+ * reduced there; 40 bytes per face come back.  Needs no embedder: the chip geometry is dlib's mean face shape with a 150-pixel chip
+ * and 0.25 padding -- what a dlib embedder file loads -- whichever embedder the context holds. */
+int32_t pvf_face_quality(pvf_handle ctx, const pvf_handle* frames, const int32_t* pts /* n*68*2 */, int32_t n, int64_t* out /* n*5 */);
+/* The contact sheet: uint8 RGB [H][W][3] to host memory, filled with `background` (r | g << 8 | b << 16); chip i, resampled to S x S
+ * (FACES.md "Tile"; S = 150 is the chip itself), with its top-left corner at (xy[2 i], xy[2 i + 1]) -- any int32, clipped to the sheet,
+ * a later tile over an earlier one; then the RECT / LINE / TEXT primitives in list order over the tiles, drawn as the renderer above
+ * draws them.  n = 0 gives background and primitives.  Refused: S outside PVF_SHEET_MIN_TILE .. PVF_SHEET_MAX_TILE, W or H below 1 or
+ * beyond PVF_SHEET_MAX_SIDE, W x H beyond PVF_SHEET_MAX_PIXELS, n beyond PVF_SHEET_MAX_TILES, a background above 0xffffff, a
+ * redaction or an unknown primitive, a list or a text pool beyond the PVF_RENDER_MAX_* caps, a text run outside the pool. */
+int32_t pvf_chip_sheet(pvf_handle ctx, const uint8_t* chips, int32_t n, const int32_t* xy /* n*2 */, int32_t S, int32_t W, int32_t H,
+                       uint32_t background, const pvf_prim* prims, int32_t n_prims, const uint8_t* text, int64_t text_bytes, uint8_t* rgb);
+/* the same sheet with the chips made on the device from frames and landmarks (the geometry of the face quality call) */
+int32_t pvf_face_sheet(pvf_handle ctx, const pvf_handle* frames, const int32_t* pts /* n*68*2 */, int32_t n, const int32_t* xy, int32_t S,
+                       int32_t W, int32_t H, uint32_t background, const pvf_prim* prims, int32_t n_prims, const uint8_t* text,
+                       int64_t text_bytes, uint8_t* rgb);
 
 /* ---- num_jitters (JITTER.md) ------------------------------------------------------------------------
  * dlib: compute_face_descriptor(img, shape, num_jitters) -- the descriptor is the fp32 mean of the network's outputs on J = num_jitters

@@ -280,6 +280,12 @@ std::map<std::string, Tensor> read_embedder(const char* path)
 
 } // namespace
 
+// dlib's mean face shape as an embedder file carries it (emb.mean_shape, 51 x 2): what faces.hip aligns chips with when no embedder is loaded
+void dlib_mean_face_shape(float* out)
+{
+    for (int i = 0; i < 51; ++i) { out[2 * i] = (float)MEAN_X[i]; out[2 * i + 1] = (float)MEAN_Y[i]; }
+}
+
 // model file given by path: `.pvfm` container or dlib `.dat` stream; kind 1 = shape predictor, 2 = embedder
 std::map<std::string, Tensor> pvf_read_model(const char* path, int kind)
 {

@@ -407,6 +407,7 @@ void jitter_embed_dev(Ctx* c, const uint8_t* d_chips, int n, int J, uint64_t see
 void ert_run(Ctx* c, const std::vector<Frame>& frames, const pvf_rect_i32* boxes, int n, int32_t* pts);
 // embedding (resnet.hip)
 void face_chip_details(const EmbedModel& m, const int32_t* pts68, ChipDetails* out);
+void dlib_mean_face_shape(float* out /* 51*2 */);      // dlibdat.hip: the shape compiled into dlib, as an embedder file's emb.mean_shape
 void resnet_forward(Ctx* c, const uint8_t* d_chips, int n, float* h_out);
 // a layer's weights on the device as the convolution kernels read them: w [cout][cin][k][k] -> d_w ([cout][K padded to 32], k = (r, s, c)
 // with the 3-channel layer's fourth all-zero channel), w_exp, and bias / gamma / beta; conv_layer_free releases everything the layer holds

@@ -92,6 +92,11 @@ _SIGS = {
     "pvf_landmarks_embed": (C.c_int32, [H, P, P, C.c_int32, P, P]),
     "pvf_embed_chips": (C.c_int32, [H, P, C.c_int32, P]),
     "pvf_face_chips": (C.c_int32, [H, P, P, C.c_int32, P]),
+    # the faces verb (FACES.md): chip quality and the contact sheet
+    "pvf_chip_quality": (C.c_int32, [H, P, C.c_int32, P]),
+    "pvf_face_quality": (C.c_int32, [H, P, P, C.c_int32, P]),
+    "pvf_chip_sheet": (C.c_int32, [H, P, C.c_int32, P, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, P, C.c_int32, P, C.c_int64, P]),
+    "pvf_face_sheet": (C.c_int32, [H, P, P, C.c_int32, P, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, P, C.c_int32, P, C.c_int64, P]),
     # num_jitters (JITTER.md): compute_face_descriptor(img, shape, num_jitters)
     "pvf_jitter_plan": (C.c_int32, [C.c_int32, C.c_uint64, P]),
     "pvf_debug_jitter_chips": (C.c_int32, [H, P, C.c_int32, C.c_int32, C.c_uint64, P]),

@@ -12,6 +12,9 @@
     python -m pyannote_video_amd demo    [--height 400] [--from 0] [--until T] [--shift 0] [--landmark PATH] [--label PATH] <video> <tracking> <output>
     python -m pyannote_video_amd redact  [--height 0] [--from 0] [--until T] [--shift 0] [--label PATH] [--only A,B | --keep A,B] [--pad 25] [--cells 8]
                                          [--shape ellipse|box] [--mode mosaic|smooth|fill] [--colour r,g,b] [--draw] <video> <tracking> <output>
+    python -m pyannote_video_amd faces   [--per 4] [--tile 150] [--columns C] [--label PATH] [--only A,B] [--spread 1.0] [--min-size 0]
+                                         [--max-dark 0.25] [--max-bright 0.25] [--from 0] [--until T] [--index PATH] [--quality PATH]
+                                         <video> <tracking> <landmarks> <output>
 
 `track` and `extract` take the reference's arguments and options and write byte-compatible files (track.txt, landmarks.txt,
 embedding.txt: formats.py).  `cluster` is the verb BASELINE.json's north_star names; the reference offers clustering through the API
@@ -24,6 +27,10 @@ drawing and RGB -> YUV 4:2:0 run in one kernel on the GPU (DEMO.md states every 
 Hershey).  Audio is not carried: the reference hands the source's audio track to moviepy, a Y4M stream has none.
 `redact` (no reference verb; REDACT.md) writes the same stream with the faces of the chosen tracks pixelated, blended or filled: a cell-mean
 reduction on the GPU in front of the same kernel.  It hides what the tracking file holds; a face the detector never found stays visible.
+
+`faces` (no reference verb; FACES.md) writes a contact sheet -- for every track, or with --label every cluster or name, its few best
+faces side by side -- as a binary PPM (a `.ppm` path, or `-` for stdout) or a `.npy` array: who is cluster 7?  Best is computed on the
+GPU, a sharpness and exposure reduction over every face chip of the film; the sheet is composed there too.
 
 <video>: no codec is linked (reference video.py:345-406 runs ffmpeg); the verbs read what a decoder writes --
   * a YUV4MPEG2 file (`.y4m`, or any file that starts with `YUV4MPEG2`): 8-bit 4:2:0 / 4:2:2 / 4:4:4, memory mapped, frame rate from
@@ -558,6 +565,149 @@ def redact(video, tracking, output, height=0, t_from=0.0, t_until=None, shift=0.
     return res
 
 
+def faces(video, tracking, landmarks, output, per=4, tile=150, columns=None, label=None, only=None, spread=1.0, min_size=0.0, max_dark=0.25,
+          max_bright=0.25, t_from=0.0, t_until=None, index=None, quality=None, ctx=None, batch=2048, ahead=96):
+    """The contact sheet of the best faces of every track, or with `label` of every cluster or name (FACES.md).  Two passes over the
+    video.  Pass 1 is `extract`'s loop: a reader thread pushes the frames that carry faces through the pinned ingest ring, this thread
+    asks for the quality sums of `batch` faces per library call (the chips are made and reduced on the device; 40 bytes a face come
+    back).  The choice is made here (faces.py).  Pass 2 reads only the frames of the chosen faces and makes one sheet call.  Returns
+    {"width", "height", "groups", "faces", "shown"}."""
+    import queue
+    import threading
+    from . import faces as _faces, render, runtime
+    ctx = ctx or runtime.default_context()
+    if not (str(output) == "-" or str(output).endswith((".ppm", ".npy"))):
+        raise ValueError("faces: the output is a .ppm or .npy path, or - for a PPM on stdout")
+    if not _faces.MIN_TILE <= int(tile) <= _faces.MAX_TILE:
+        raise ValueError("faces: --tile is %d .. %d" % (_faces.MIN_TILE, _faces.MAX_TILE))
+    if int(per) < 1:
+        raise ValueError("faces: --per is at least 1")
+    frame_width, frame_height = video.frame_size
+    rows = formats.read_tracks(tracking) if isinstance(tracking, str) else tracking
+    marks = formats.read_landmarks(landmarks) if isinstance(landmarks, str) else landmarks
+    labels = render.read_labels(label) if isinstance(label, str) else label
+    all_faces = _faces.landmark_faces(rows, marks, [t for t, _ in _times(video)], frame_width, frame_height)
+    by_frame = {}
+    for i, f in enumerate(all_faces):
+        by_frame.setdefault(f[2], []).append(i)
+    sums = np.zeros((len(all_faces), 5), np.int64)
+
+    # ---- pass 1: the quality of every face
+    last_wanted = max(by_frame) if by_frame else -1
+    q = queue.Queue(maxsize=max(2, int(ahead)))
+    state = {"error": None}
+
+    def reader():
+        stager = runtime.HostFrameStager(ctx, 16)
+        try:
+            for fi, (t, rgb) in enumerate(video):
+                if fi > last_wanted or state["error"] is not None:
+                    break
+                if fi not in by_frame:
+                    continue
+                rgb, owned = stager.stage(rgb)
+                q.put((fi, rgb, owned))
+            stager.close()
+        except BaseException as e:          # noqa: BLE001 -- re-raised below
+            state["error"] = e
+        finally:
+            q.put(None)
+
+    th = threading.Thread(target=reader, name="pvface-faces-reader")
+    th.start()
+    try:
+        pend_f, pend_i, pend_own = [], [], []
+
+        def flush():
+            if pend_i:
+                sums[pend_i] = ctx.face_quality(pend_f, np.stack([all_faces[i][4] for i in pend_i]))
+            for f in pend_own:
+                f.release()
+            del pend_f[:], pend_i[:], pend_own[:]
+        while state["error"] is None:
+            item = q.get()
+            if item is None:
+                break
+            fi, dev, owned = item
+            if owned:
+                pend_own.append(dev)
+            for i in by_frame[fi]:
+                pend_f.append(dev); pend_i.append(i)
+            if len(pend_i) >= batch:
+                flush()
+        if state["error"] is None:
+            flush()
+    except BaseException as e:              # noqa: BLE001 -- re-raised below
+        state["error"] = state["error"] or e
+    finally:
+        while th.is_alive():                 # an error on this side: let the reader run out
+            try:
+                q.get(timeout=0.05)
+            except queue.Empty:
+                pass
+        th.join()
+    if state["error"] is not None:
+        raise state["error"]
+
+    # ---- the choice
+    sym = [_faces.symmetry(f[4]) for f in all_faces]
+    sc = [_faces.score(sums[i], sym[i]) for i in range(len(all_faces))]
+    ok = [_faces.eligible(sums[i], f[3][3] - f[3][1], frame_height, max_dark, max_bright, min_size) for i, f in enumerate(all_faces)]
+    if quality:
+        with open(quality, "w") as fq:
+            for i, f in enumerate(all_faces):
+                fq.write(_faces.quality_line(f[0], f[1], sums[i], sym[i], sc[i], ok[i]))
+    groups = _faces.group_faces(all_faces, labels, only, t_from, t_until)
+    if not groups:
+        raise ValueError("faces: no face to show (an empty landmark file, or --only / --from / --until leave none)")
+    shown = []
+    for name, colour, idx in groups:
+        pick = _faces.choose([(sc[i], all_faces[i][0], all_faces[i][1], ok[i]) for i in idx], int(per), spread)
+        shown.append([idx[k] for k in pick])
+    cols = int(columns) if columns else _faces.default_columns(len(groups))
+    W, H, corners, prims = _faces.layout([(g[0], g[1], len(s)) for g, s in zip(groups, shown)], int(per), int(tile), cols)
+    flat = [i for s in shown for i in s]
+    _faces.check_sheet(W, H, len(flat), len(prims))
+    if index:
+        with open(index, "w") as fx:
+            for g, s in zip(groups, shown):
+                for rank, i in enumerate(s):
+                    fx.write("%s %d " % (g[0], rank) + _faces.quality_line(all_faces[i][0], all_faces[i][1], sums[i], sym[i], sc[i], ok[i]))
+
+    # ---- pass 2: the frames of the chosen faces, one sheet call
+    need = sorted(set(all_faces[i][2] for i in flat))
+    stager = runtime.HostFrameStager(ctx, max(2, min(len(need), 16)))
+    dev, own = {}, []
+    try:
+        if hasattr(video, "frame"):
+            source = ((fi, video.frame(fi)) for fi in need)
+        else:
+            wanted = set(need)
+            source = ((fi, frame) for fi, (_, frame) in enumerate(video) if fi in wanted)
+        for fi, frame in source:
+            d, owned = stager.stage(frame)
+            dev[fi] = d
+            if owned:
+                own.append(d)
+            if len(dev) == len(need):
+                break
+        stager.close()
+        sheet = ctx.face_sheet([dev[all_faces[i][2]] for i in flat], np.stack([all_faces[i][4] for i in flat]),
+                               [xy for c in corners for xy in c], int(tile), W, H, _faces.BACKGROUND, prims)
+    finally:
+        for d in own:
+            d.release()
+    if str(output) == "-":
+        sys.stdout.buffer.write(_faces.ppm_bytes(sheet))
+        sys.stdout.buffer.flush()
+    elif str(output).endswith(".npy"):
+        np.save(output, sheet)
+    else:
+        with open(output, "wb") as fo:
+            fo.write(_faces.ppm_bytes(sheet))
+    return {"width": W, "height": H, "groups": [g[0] for g in groups], "faces": len(all_faces), "shown": len(flat)}
+
+
 def _names(text):
     return set(n for n in text.split(",") if n)
 
@@ -665,6 +815,22 @@ def _parser():
     rd.add_argument("--mode", choices=("mosaic", "smooth", "fill"), default="mosaic")
     rd.add_argument("--colour", type=_colour, default=(0, 0, 0), metavar="r,g,b", help="the fill colour")
     rd.add_argument("--draw", action="store_true", help="draw what `demo` draws on top of the redactions")
+    fc = sub.add_parser("faces", help="a contact sheet of the best faces of every track, cluster or name, as PPM or .npy")
+    fc.add_argument("video"); fc.add_argument("tracking"); fc.add_argument("landmarks", help="landmarks.txt of `extract`")
+    fc.add_argument("output", help="a .ppm or .npy path, or - for a PPM on stdout")
+    fc.add_argument("--per", type=int, default=4, help="faces shown per group")
+    fc.add_argument("--tile", type=int, default=150, help="side of a face on the sheet, 48 .. 600 (150: the aligned chip itself)")
+    fc.add_argument("--columns", type=int, default=None, help="panels per row (default: 1 up to 24 groups, then ceil(groups / 24))")
+    fc.add_argument("--label", default=None, help="`identifier name` lines, what `cluster` and `identify` write: a group per name")
+    fc.add_argument("--only", type=_names, default=None, metavar="A,B", help="show only these groups (names; #7 or 7 for a track)")
+    fc.add_argument("--spread", type=float, default=1.0, help="seconds between two shown faces of one track, while others are left")
+    fc.add_argument("--min-size", type=float, default=0.0, help="smallest box height, as a share of the frame height, of an eligible face")
+    fc.add_argument("--max-dark", type=float, default=0.25, help="largest share of pixels with luma <= 16 of an eligible face")
+    fc.add_argument("--max-bright", type=float, default=0.25, help="largest share of pixels with luma >= 239 of an eligible face")
+    fc.add_argument("--from", dest="t_from", type=float, default=0.0, help="start, seconds")
+    fc.add_argument("--until", dest="t_until", type=float, default=None, help="end, seconds (default: the video's duration)")
+    fc.add_argument("--index", default=None, help="write `group rank T track S1 S2 SY ND NB sym score eligible` per shown face")
+    fc.add_argument("--quality", default=None, help="write `T track S1 S2 SY ND NB sym score eligible` for every face of the film")
     return ap
 
 
@@ -684,6 +850,9 @@ def main(argv=None):
     res = None
 
     def video():
+        if a.video == "-" and a.verb == "faces":
+            ap.error("faces reads the video twice, once for the quality of every face and once for the frames of the chosen ones: "
+                     "give it a file, not a stream on stdin")
         if a.video == "-" and a.verb not in ("track", "process"):
             ap.error("%s needs the length of the video: give it a file, not a stream on stdin" % a.verb)
         over = {}
@@ -728,6 +897,13 @@ def main(argv=None):
                      keep=a.keep, pad=a.pad, cells=a.cells, shape=a.shape, mode=a.mode, colour=a.colour, draw=a.draw,
                      matrix=a.matrix or getattr(v, "matrix", "601"),
                      full_range=(a.range == "full") if a.range is not None else bool(getattr(v, "full_range", False)), fps=a.fps, ctx=ctx)
+    elif a.verb == "faces":
+        try:
+            res = faces(video(), a.tracking, a.landmarks, a.output, per=a.per, tile=a.tile, columns=a.columns, label=a.label, only=a.only,
+                        spread=a.spread, min_size=a.min_size, max_dark=a.max_dark, max_bright=a.max_bright, t_from=a.t_from, t_until=a.t_until,
+                        index=a.index, quality=a.quality, ctx=ctx)
+        except ValueError as e:
+            ap.error(str(e))
     elif a.verb == "extract":
         extract(video(), a.landmark_model, a.embedding_model, a.tracking, a.landmarks, a.embeddings, ctx=ctx, num_jitters=a.jitters,
                 jitter_seed=a.jitter_seed)

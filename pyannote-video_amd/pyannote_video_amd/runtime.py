@@ -740,6 +740,59 @@ class Context(object):
             check(self._l.pvf_face_chips(self._h, ptr(self._handles(frames)), ptr(pts), n, ptr(out)))
         return out
 
+    # ---- the faces verb (FACES.md)
+    def chip_quality(self, chips):
+        """int64 [n, 5] = S1, S2, SY, ND, NB of uint8 [n, 150, 150, 3] chips (pvf_chip_quality): the sums faces.score reads"""
+        chips = np.ascontiguousarray(chips, np.uint8).reshape(-1, 150, 150, 3)
+        out = np.zeros((len(chips), 5), np.int64)
+        check(self._l.pvf_chip_quality(self._h, ptr(chips), len(chips), ptr(out)))
+        return out
+
+    def face_quality(self, frames, pts):
+        """the same five sums for faces given by frame and landmarks: the chips are made and reduced on the device (pvf_face_quality);
+        needs no embedder"""
+        pts = np.ascontiguousarray(pts, np.int32).reshape(-1, 68, 2)
+        out = np.zeros((len(pts), 5), np.int64)
+        with self._staging():
+            check(self._l.pvf_face_quality(self._h, ptr(self._handles(frames)), ptr(pts), len(pts), ptr(out)))
+        return out
+
+    @staticmethod
+    def _sheet_args(n, xy, background, prims):
+        from . import render as _render
+        xy = np.ascontiguousarray(xy, np.int32).reshape(-1, 2)
+        if len(xy) != n:
+            raise ValueError("%d tile corners for %d chips" % (len(xy), n))
+        _, p, text = _render.pack_primitives([list(prims)])
+        r, g, b = (int(v) for v in background)
+        return xy, r | g << 8 | b << 16, p, text
+
+    @staticmethod
+    def _sheet_out(width, height):
+        """the picture's memory, or None for a size the library refuses (it says why)"""
+        w, h = int(width), int(height)
+        return np.empty((h, w, 3), np.uint8) if 0 < w <= 16384 and 0 < h <= 16384 and w * h <= 1 << 26 else None
+
+    def chip_sheet(self, chips, xy, S, width, height, background=(0, 0, 0), prims=()):
+        """uint8 [height, width, 3]: the chips resampled to S x S at the corners xy (later over earlier), the primitives over them
+        (pvf_chip_sheet; FACES.md "Sheet")"""
+        chips = np.ascontiguousarray(chips, np.uint8).reshape(-1, 150, 150, 3)
+        xy, bg, p, text = self._sheet_args(len(chips), xy, background, prims)
+        out = self._sheet_out(width, height)
+        check(self._l.pvf_chip_sheet(self._h, ptr(chips), len(chips), ptr(xy), int(S), int(width), int(height), bg, ptr(p), len(p), ptr(text),
+                                     len(text), ptr(out)))
+        return out
+
+    def face_sheet(self, frames, pts, xy, S, width, height, background=(0, 0, 0), prims=()):
+        """chip_sheet with the chips made on the device from frames and landmarks (pvf_face_sheet)"""
+        pts = np.ascontiguousarray(pts, np.int32).reshape(-1, 68, 2)
+        xy, bg, p, text = self._sheet_args(len(pts), xy, background, prims)
+        out = self._sheet_out(width, height)
+        with self._staging():
+            check(self._l.pvf_face_sheet(self._h, ptr(self._handles(frames)), ptr(pts), len(pts), ptr(xy), int(S), int(width), int(height), bg,
+                                         ptr(p), len(p), ptr(text), len(text), ptr(out)))
+        return out
+
     def embed_chips(self, chips, num_jitters=0, seed=0):
         chips = np.ascontiguousarray(chips, np.uint8).reshape(-1, 150, 150, 3)
         out = np.zeros((len(chips), 128), np.float32)
