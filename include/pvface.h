@@ -300,6 +300,21 @@ int32_t pvf_face_sheet(pvf_handle ctx, const pvf_handle* frames, const int32_t* 
                        int32_t W, int32_t H, uint32_t background, const pvf_prim* prims, int32_t n_prims, const uint8_t* text,
                        int64_t text_bytes, uint8_t* rgb);
 
+/* ---- talk: how much the mouth of a face chip moved since the face before it (TALK.md; no reference call) -------- */
+#define PVF_MOTION_MAX_FACES 32768          /* 32768 x 2 x 46 x 72 B of patches = 217 MB */
+/* Eight int32 per face: DM0, DMmin, kM, DC0, DCmin, kC, SM, NZ.  prev[i] is -1 or an index < i of the same call: the face that
+ * face i is compared with; several faces may name the same one.  D(dy, dx) is the sum over a window of 40 rows x 64 columns of the chip's
+ * luma Y = (77 R + 150 G + 29 B + 128) >> 8 of |Y_i(r, c) - Y_prev(r + dy, c + dx)|, for the 49 shifts in [-3, 3]^2; the mouth window
+ * is rows 94 .. 133, the control window rows 52 .. 91, both columns 42 .. 105.  D?0 = D(0, 0), D?min the minimum over the shifts, k? =
+ * (dy + 3) * 7 + (dx + 3) of the first minimum in row-major order, but 24 when D(0, 0) is the minimum.  SM = sum of Y over the mouth
+ * window, NZ = #{Y <= 16} over both windows.  A face with prev[i] = -1 has -1 in the first six.  Integer sums: nothing depends on the
+ * shape of a reduction or on the rounds of 4096 the host chips go through the device in.  n = 0 does nothing; refused: n < 0 or beyond
+ * PVF_MOTION_MAX_FACES, null pointers with n > 0, prev[i] < -1, prev[i] >= i. */
+int32_t pvf_chip_motion(pvf_handle ctx, const uint8_t* chips, int32_t n, const int32_t* prev, int32_t* out /* n*8 */);
+/* the same eight values for faces given by frame and 68 landmarks: the chips are made on the device with the geometry of the face
+ * quality call (no embedder needed) and reduced there; 32 bytes per face come back. */
+int32_t pvf_face_motion(pvf_handle ctx, const pvf_handle* frames, const int32_t* pts /* n*68*2 */, int32_t n, const int32_t* prev, int32_t* out /* n*8 */);
+
 /* ---- num_jitters (JITTER.md) ------------------------------------------------------------------------
  * dlib: compute_face_descriptor(img, shape, num_jitters) -- the descriptor is the fp32 mean of the network's outputs on J = num_jitters
  * perturbed copies of the aligned chip (shift, zoom, rotation, mirror).  The transform of jitter j is a function of (seed, j) alone,

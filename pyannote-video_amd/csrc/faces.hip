@@ -235,7 +235,7 @@ __global__ void __launch_bounds__(256) sheet_prims_k(const SheetPrimArgs a)
 // ---------------------------------------------------------------------------------------------------
 // the chip geometry: dlib's compiled-in mean face shape with EmbedModel's defaults (150, 0.25) -- what a dlib embedder file loads.  Not
 // the loaded embedder's: the verb runs without one, and a face's quality must not depend on what else the context holds.
-static const EmbedModel& faces_geometry()
+const EmbedModel& faces_geometry()
 {
     static const EmbedModel dflt = [] {
         EmbedModel e;
@@ -247,7 +247,7 @@ static const EmbedModel& faces_geometry()
 }
 
 // the aligned chips of m faces into d_chips (the plan of api.hip's make_face_chips, without its need of a loaded embedder)
-static void faces_make_chips(Ctx* c, const pvf_handle* frames, const int32_t* pts, int m, uint8_t* d_chips)
+void faces_make_chips(Ctx* c, const pvf_handle* frames, const int32_t* pts, int m, uint8_t* d_chips)
 {
     const EmbedModel& e = faces_geometry();
     static_assert(Q_SIDE == 150, "EmbedModel's default chip size");
@@ -268,9 +268,6 @@ static void quality_launch(Ctx* c, const uint8_t* d_chips, int m, int64_t* d_out
     HIP_CHECK(hipGetLastError());
 }
 
-// chips_host, or frames + pts: where the chips of a call come from
-struct ChipSource { const uint8_t* host; const pvf_handle* frames; const int32_t* pts; };
-
 static void check_source(const ChipSource& src, int n, const std::string& w)
 {
     PVF_REQUIRE(n >= 0 && n <= PVF_SHEET_MAX_TILES, w + ": n outside 0 .. PVF_SHEET_MAX_TILES");
@@ -278,7 +275,7 @@ static void check_source(const ChipSource& src, int n, const std::string& w)
 }
 
 // round [i0, i0 + m) of the source into d_chips, behind whatever still reads d_chips on the stream
-static void source_round(Ctx* c, const ChipSource& src, int i0, int m, uint8_t* d_chips)
+void faces_source_round(Ctx* c, const ChipSource& src, int i0, int m, uint8_t* d_chips)
 {
     if (src.host) HIP_CHECK(hipMemcpyAsync(d_chips, src.host + (size_t)i0 * Q_BYTES, (size_t)m * Q_BYTES, hipMemcpyHostToDevice, c->stream));
     else faces_make_chips(c, src.frames + i0, src.pts + (size_t)i0 * 136, m, d_chips);
@@ -296,7 +293,7 @@ static void quality_run(Ctx* c, const ChipSource& src, int n, int64_t* out, cons
     c->s_act0.ensure(out_lay.bytes());
     for (int i0 = 0; i0 < n; i0 += Q_ROUND) {
         const int m = std::min(Q_ROUND, n - i0);
-        source_round(c, src, i0, m, sChips.in(c->s_trk0));
+        faces_source_round(c, src, i0, m, sChips.in(c->s_trk0));
         quality_launch(c, sChips.in(c->s_trk0), m, sOut.in(c->s_act0) + (size_t)i0 * 5);
     }
     HIP_CHECK(hipMemcpyAsync(out, sOut.in(c->s_act0), sOut.bytes(), hipMemcpyDeviceToHost, c->stream));
@@ -342,7 +339,7 @@ static void sheet_run(Ctx* c, const ChipSource& src, int n, const int32_t* xy, i
     // rounds in list order; a later round stores only where its own tiles are, so the last tile of the whole list wins
     for (int i0 = 0; i0 == 0 || i0 < n; i0 += Q_ROUND) {
         const int m = std::min(Q_ROUND, n - i0);
-        if (m) source_round(c, src, i0, m, sChips.in(c->s_trk0));
+        if (m) faces_source_round(c, src, i0, m, sChips.in(c->s_trk0));
         SheetTileArgs a;
         a.chips = sChips.in(c->s_trk0); a.xy = sXy.in(c->s_act0) + (size_t)i0 * 2;
         a.n = m; a.S = S; a.W = W; a.H = H; a.background = background; a.fill = i0 == 0; a.rgb = sRgb.in(c->s_act0);

@@ -409,6 +409,11 @@ void ert_run(Ctx* c, const std::vector<Frame>& frames, const pvf_rect_i32* boxes
 void face_chip_details(const EmbedModel& m, const int32_t* pts68, ChipDetails* out);
 void dlib_mean_face_shape(float* out /* 51*2 */);      // dlibdat.hip: the shape compiled into dlib, as an embedder file's emb.mean_shape
 void resnet_forward(Ctx* c, const uint8_t* d_chips, int n, float* h_out);
+// the faces and talk verbs' chips (faces.hip): dlib's compiled-in mean shape, a 150-pixel chip, padding 0.25; no embedder needed
+struct ChipSource { const uint8_t* host; const pvf_handle* frames; const int32_t* pts; };      // host chips, or frames + landmarks
+const EmbedModel& faces_geometry();
+void faces_make_chips(Ctx* c, const pvf_handle* frames, const int32_t* pts, int m, uint8_t* d_chips);
+void faces_source_round(Ctx* c, const ChipSource& src, int i0, int m, uint8_t* d_chips);       // chips [i0, i0 + m) of the source, on c->stream
 // a layer's weights on the device as the convolution kernels read them: w [cout][cin][k][k] -> d_w ([cout][K padded to 32], k = (r, s, c)
 // with the 3-channel layer's fourth all-zero channel), w_exp, and bias / gamma / beta; conv_layer_free releases everything the layer holds
 void conv_layer_upload(ConvLayer& L, const float* w, const float* bias, const float* gamma, const float* beta);

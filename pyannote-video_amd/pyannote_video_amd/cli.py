@@ -15,6 +15,8 @@
     python -m pyannote_video_amd faces   [--per 4] [--tile 150] [--columns C] [--label PATH] [--only A,B] [--spread 1.0] [--min-size 0]
                                          [--max-dark 0.25] [--max-bright 0.25] [--from 0] [--until T] [--index PATH] [--quality PATH]
                                          <video> <tracking> <landmarks> <output>
+    python -m pyannote_video_amd talk    [--window 0.4] [--on 3.0] [--off 1.5] [--min-duration 0.3] [--max-pause 0.3] [--max-dark 0.25]
+                                         [--from 0] [--until T] [--label PATH] [--segments PATH] <video> <tracking> <landmarks> <output>
 
 `track` and `extract` take the reference's arguments and options and write byte-compatible files (track.txt, landmarks.txt,
 embedding.txt: formats.py).  `cluster` is the verb BASELINE.json's north_star names; the reference offers clustering through the API
@@ -31,12 +33,15 @@ reduction on the GPU in front of the same kernel.  It hides what the tracking fi
 `faces` (no reference verb; FACES.md) writes a contact sheet -- for every track, or with --label every cluster or name, its few best
 faces side by side -- as a binary PPM (a `.ppm` path, or `-` for stdout) or a `.npy` array: who is cluster 7?  Best is computed on the
 GPU, a sharpness and exposure reduction over every face chip of the film; the sheet is composed there too.
+`talk` (no reference verb; TALK.md) writes one line per face with how much its mouth moved since the frame before -- displaced absolute
+differences of the aligned chip's mouth window, less those of a control window above it, computed on the GPU -- and, with --segments,
+the spans in which a track is taken to be talking: a stated rule with untuned thresholds on top of the per-face columns.
 
 <video>: no codec is linked (reference video.py:345-406 runs ffmpeg); the verbs read what a decoder writes --
   * a YUV4MPEG2 file (`.y4m`, or any file that starts with `YUV4MPEG2`): 8-bit 4:2:0 / 4:2:2 / 4:4:4, memory mapped, frame rate from
     its header (`ffmpeg -i film.mkv -pix_fmt yuv420p -f yuv4mpegpipe film.y4m`); the planes go to the GPU as they are and are
     converted to RGB there (--matrix 601|709, --range limited|full override the header);
-  * `-`: the same stream from stdin, for the verbs that read the video once and need no length (`track`, `process`):
+  * `-`: the same stream from stdin, for the verbs that read the video once and need no length (`track`, `process`, `talk`):
     `ffmpeg -i film.mkv -pix_fmt yuv420p -f yuv4mpegpipe - | python -m pyannote_video_amd process - ...`;
   * a `.npy` file holding uint8 [N, H, W, 3] RGB frames (memory mapped; frame rate from --fps);
   * the bench's synthetic clip: `synthetic:<width>x<height>x<frames>[:shots[:faces[:seed]]]`.
@@ -708,6 +713,125 @@ def faces(video, tracking, landmarks, output, per=4, tile=150, columns=None, lab
     return {"width": W, "height": H, "groups": [g[0] for g in groups], "faces": len(all_faces), "shown": len(flat)}
 
 
+def talk(video, tracking, landmarks, output, window=0.4, on=3.0, off=1.5, min_duration=0.3, max_pause=0.3, max_dark=0.25, t_from=0.0,
+         t_until=None, label=None, segments=None, ctx=None, batch=2048, ahead=96):
+    """Lip activity of every face and the spans in which a track is taken to be talking (TALK.md).  One pass over the video, pass 1 of
+    `faces`: a reader thread pushes the frames that carry faces through the pinned ingest ring, this thread asks for the eight motion
+    integers of a batch of whole frames per library call (chips, patches and sums are made on the device; 32 bytes a face come back).
+    A face is compared with the face of its track on the frame before; the last frame of a batch is kept alive and leads the next
+    call, its faces without a predecessor and their rows discarded, so links cross batches.  The rest is talk.py.  Returns {"faces",
+    "linked", "segments"}."""
+    import queue
+    import threading
+    from . import faces as _faces, render, runtime, talk as _talk
+    ctx = ctx or runtime.default_context()
+    if int(batch) < 1:
+        raise ValueError("talk: a batch holds at least one face")
+    frame_width, frame_height = video.frame_size
+    rows = formats.read_tracks(tracking) if isinstance(tracking, str) else tracking
+    marks = formats.read_landmarks(landmarks) if isinstance(landmarks, str) else landmarks
+    labels = render.read_labels(label) if isinstance(label, str) else label
+    try:
+        n_frames = len(video)
+    except TypeError:                        # a stream: as many frame times as the tracking file needs
+        n_frames = int(max([r[0] for r in rows] or [0.0]) * video.frame_rate) + 2
+    times = [i / video.frame_rate for i in range(n_frames)]
+    all_faces = [f for f in _faces.landmark_faces(rows, marks, times, frame_width, frame_height)
+                 if f[0] >= t_from and (t_until is None or f[0] < t_until)]
+    prev = _talk.link([(f[2], f[1]) for f in all_faces])
+    by_frame = {}
+    for i, f in enumerate(all_faces):
+        by_frame.setdefault(f[2], []).append(i)
+    out = np.full((len(all_faces), 8), -1, np.int32)
+
+    last_wanted = max(by_frame) if by_frame else -1
+    q = queue.Queue(maxsize=max(2, int(ahead)))
+    state = {"error": None}
+
+    def reader():
+        stager = runtime.HostFrameStager(ctx, 16)
+        try:
+            if last_wanted >= 0:
+                for fi, (t, rgb) in enumerate(video):
+                    if fi > last_wanted or state["error"] is not None:
+                        break
+                    if fi not in by_frame:
+                        continue
+                    rgb, owned = stager.stage(rgb)
+                    q.put((fi, rgb, owned))
+            stager.close()
+        except BaseException as e:          # noqa: BLE001 -- re-raised below
+            state["error"] = e
+        finally:
+            q.put(None)
+
+    th = threading.Thread(target=reader, name="pvface-talk-reader")
+    th.start()
+    carry = []                               # the last frame of the batch before: [(frame index, device frame, owned)]
+    try:
+        pend = []
+
+        def flush():
+            frames, idx = [], []
+            for fi, dev, _ in carry + pend:
+                for i in by_frame[fi]:
+                    frames.append(dev); idx.append(i)
+            lead = sum(len(by_frame[fi]) for fi, _, _ in carry)
+            local = dict((i, k) for k, i in enumerate(idx))
+            p = [-1 if k < lead else local.get(prev[i], -1) for k, i in enumerate(idx)]
+            got = ctx.face_motion(frames, np.stack([all_faces[i][4] for i in idx]), p)
+            out[idx[lead:]] = got[lead:]
+            for _, dev, owned in carry + pend[:-1]:
+                if owned:
+                    dev.release()
+            carry[:] = pend[-1:]
+            del pend[:]
+        while state["error"] is None:
+            item = q.get()
+            if item is None:
+                break
+            pend.append(item)
+            if sum(len(by_frame[fi]) for fi, _, _ in pend) >= batch:
+                flush()
+        if state["error"] is None and pend:
+            flush()
+    except BaseException as e:              # noqa: BLE001 -- re-raised below
+        state["error"] = state["error"] or e
+    finally:
+        while th.is_alive():                 # an error on this side: let the reader run out
+            try:
+                item = q.get(timeout=0.05)
+                if item is not None:
+                    pend.append(item)
+            except queue.Empty:
+                pass
+        th.join()
+        while not q.empty():
+            item = q.get()
+            if item is not None:
+                pend.append(item)
+        for _, dev, owned in carry + pend:
+            if owned:
+                dev.release()
+    if state["error"] is not None:
+        raise state["error"]
+
+    linked = [p >= 0 for p in prev]
+    per, segs = _talk.analyse([(f[0], f[1], f[4]) for f in all_faces], out, linked, window, on, off, min_duration, max_pause, max_dark)
+    text = "".join(_talk.face_line(f[0], f[1], out[i], *per[i]) for i, f in enumerate(all_faces))
+    if str(output) == "-":
+        sys.stdout.write(text)
+        sys.stdout.flush()
+    else:
+        with open(output, "w") as fo:
+            fo.write(text)
+    if segments:
+        with open(segments, "w") as fs:
+            for track, start, end, mean in segs:
+                fs.write(_talk.segment_line(track, start, end, mean, None if labels is None else (labels.get(track) or "#%d" % track)))
+    return {"faces": len(all_faces), "linked": int(sum(linked)), "segments": segs}
+
+
 def _names(text):
     return set(n for n in text.split(",") if n)
 
@@ -831,6 +955,19 @@ def _parser():
     fc.add_argument("--until", dest="t_until", type=float, default=None, help="end, seconds (default: the video's duration)")
     fc.add_argument("--index", default=None, help="write `group rank T track S1 S2 SY ND NB sym score eligible` per shown face")
     fc.add_argument("--quality", default=None, help="write `T track S1 S2 SY ND NB sym score eligible` for every face of the film")
+    tk = sub.add_parser("talk", help="lip activity of every face and the spans in which a track is taken to be talking")
+    tk.add_argument("video"); tk.add_argument("tracking"); tk.add_argument("landmarks", help="landmarks.txt of `extract`")
+    tk.add_argument("output", help="`T track DM0 DMmin kM DC0 DCmin kC SM NZ open a s talking` per face; - for stdout")
+    tk.add_argument("--window", type=float, default=0.4, help="seconds the activity is averaged over, centred on the face")
+    tk.add_argument("--on", type=float, default=3.0, help="smoothed activity (grey levels per pixel) at which talking turns on")
+    tk.add_argument("--off", type=float, default=1.5, help="smoothed activity below which talking turns off")
+    tk.add_argument("--min-duration", type=float, default=0.3, help="spans shorter than this many seconds are dropped")
+    tk.add_argument("--max-pause", type=float, default=0.3, help="spans of a track no more than this many seconds apart are merged")
+    tk.add_argument("--max-dark", type=float, default=0.25, help="largest share of window pixels with luma <= 16 of a valid face")
+    tk.add_argument("--from", dest="t_from", type=float, default=0.0, help="start, seconds")
+    tk.add_argument("--until", dest="t_until", type=float, default=None, help="end, seconds (default: the video's duration)")
+    tk.add_argument("--label", default=None, help="`identifier name` lines: --segments lines end in the track's name")
+    tk.add_argument("--segments", default=None, help="write `track start end mean_s` per talking span")
     return ap
 
 
@@ -853,7 +990,7 @@ def main(argv=None):
         if a.video == "-" and a.verb == "faces":
             ap.error("faces reads the video twice, once for the quality of every face and once for the frames of the chosen ones: "
                      "give it a file, not a stream on stdin")
-        if a.video == "-" and a.verb not in ("track", "process"):
+        if a.video == "-" and a.verb not in ("track", "process", "talk"):
             ap.error("%s needs the length of the video: give it a file, not a stream on stdin" % a.verb)
         over = {}
         if a.matrix is not None:
@@ -904,6 +1041,12 @@ def main(argv=None):
                         index=a.index, quality=a.quality, ctx=ctx)
         except ValueError as e:
             ap.error(str(e))
+    elif a.verb == "talk":
+        try:
+            res = talk(video(), a.tracking, a.landmarks, a.output, window=a.window, on=a.on, off=a.off, min_duration=a.min_duration,
+                       max_pause=a.max_pause, max_dark=a.max_dark, t_from=a.t_from, t_until=a.t_until, label=a.label, segments=a.segments, ctx=ctx)
+        except (KeyError, ValueError) as e:
+            ap.error(str(e.args[0]) if e.args else str(e))
     elif a.verb == "extract":
         extract(video(), a.landmark_model, a.embedding_model, a.tracking, a.landmarks, a.embeddings, ctx=ctx, num_jitters=a.jitters,
                 jitter_seed=a.jitter_seed)

@@ -757,6 +757,30 @@ class Context(object):
             check(self._l.pvf_face_quality(self._h, ptr(self._handles(frames)), ptr(pts), len(pts), ptr(out)))
         return out
 
+    # ---- the talk verb (TALK.md)
+    def chip_motion(self, chips, prev):
+        """int32 [n, 8] = DM0, DMmin, kM, DC0, DCmin, kC, SM, NZ of uint8 [n, 150, 150, 3] chips (pvf_chip_motion); prev[i] is -1 or
+        the index < i of the chip that chip i is compared with"""
+        chips = np.ascontiguousarray(chips, np.uint8).reshape(-1, 150, 150, 3)
+        prev = np.ascontiguousarray(prev, np.int32).reshape(-1)
+        if len(prev) != len(chips):
+            raise ValueError("chip_motion: one predecessor per chip")
+        out = np.zeros((len(chips), 8), np.int32)
+        check(self._l.pvf_chip_motion(self._h, ptr(chips), len(chips), ptr(prev), ptr(out)))
+        return out
+
+    def face_motion(self, frames, pts, prev):
+        """the same eight values for faces given by frame and landmarks: the chips are made and reduced on the device
+        (pvf_face_motion); needs no embedder"""
+        pts = np.ascontiguousarray(pts, np.int32).reshape(-1, 68, 2)
+        prev = np.ascontiguousarray(prev, np.int32).reshape(-1)
+        if len(prev) != len(pts) or len(frames) != len(pts):
+            raise ValueError("face_motion: one frame and one predecessor per face")
+        out = np.zeros((len(pts), 8), np.int32)
+        with self._staging():
+            check(self._l.pvf_face_motion(self._h, ptr(self._handles(frames)), ptr(pts), len(pts), ptr(prev), ptr(out)))
+        return out
+
     @staticmethod
     def _sheet_args(n, xy, background, prims):
         from . import render as _render
