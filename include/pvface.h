@@ -315,6 +315,27 @@ int32_t pvf_chip_motion(pvf_handle ctx, const uint8_t* chips, int32_t n, const i
  * quality call (no embedder needed) and reduced there; 32 bytes per face come back. */
 int32_t pvf_face_motion(pvf_handle ctx, const pvf_handle* frames, const int32_t* pts /* n*68*2 */, int32_t n, const int32_t* prev, int32_t* out /* n*8 */);
 
+/* ---- tube: square windows of resident frames as S x S pictures (TUBE.md; no reference call) -------------------- */
+#define PVF_CROP_MIN_SIZE 1              /* side S of a picture */
+#define PVF_CROP_MAX_SIZE 1024           /* (1024 S^2 x 255 < 2^38: the enlarging sums are 64-bit) */
+#define PVF_CROP_MIN_SIDE 16             /* side L of a window in sixteenths of a source pixel: one pixel */
+#define PVF_CROP_MAX_SIDE (1 << 18)      /* 16384 pixels: a row's weighted sum stays below L x 255 < 2^26, the picture's below L^2 x 255 < 2^44 */
+#define PVF_CROP_MAX_COORD (1 << 30)     /* |X0|, |Y0| in sixteenths: X0 >> 4 plus a window's pixels stays far inside int32 */
+#define PVF_CROP_MAX_CROPS 65536         /* crops of one call */
+#define PVF_CROP_YUV420 4                /* flags: planar YUV 4:2:0 pictures (default: interleaved RGB); with PVF_YUV_BT709 / PVF_YUV_FULL_RANGE */
+/* n pictures of S x S pixels, tight and in call order: picture i is the window windows[3 i .. 3 i + 2] = (X0, Y0, L) of frame frames[i],
+ * left edge, top edge and side of a square in sixteenths of a source pixel, any sign and position; outside the frame reads black.
+ * L >= 16 S: the exact area average, (sum wy wx byte + L^2 // 2) // L^2; L < 16 S: bilinear at the sample centres,
+ * (sum of four weights x bytes + 512 S^2) // (1024 S^2); TUBE.md states both, integer arithmetic throughout.  A picture is RGB [S][S][3]
+ * or, with PVF_CROP_YUV420, Y [S][S] then U and V [ceil(S / 2)]^2 of the RGB picture, converted as pvf_render_batch converts (the two
+ * colour flags mean nothing without it).  out: host memory, or with out_on_device device memory; the call is complete when it returns.
+ * Crops go through the device in rounds (32 MiB of pictures, or the crops the environment variable PVF_CROP_ROUND names, read at the
+ * call), a round's copy to the host running under the next round's kernel; nothing depends on the rounds.  n = 0 does nothing.
+ * Refused before any work: n < 0 or beyond PVF_CROP_MAX_CROPS, null pointers with n > 0, S or L outside their caps, X0 or Y0 beyond
+ * PVF_CROP_MAX_COORD, unknown flag bits, an unknown or released frame. */
+int32_t pvf_frame_crops(pvf_handle ctx, const pvf_handle* frames, const int32_t* windows /* n*3 */, int32_t n, int32_t S, int32_t flags,
+                        uint8_t* out, int32_t out_on_device);
+
 /* ---- num_jitters (JITTER.md) ------------------------------------------------------------------------
  * dlib: compute_face_descriptor(img, shape, num_jitters) -- the descriptor is the fp32 mean of the network's outputs on J = num_jitters
  * perturbed copies of the aligned chip (shift, zoom, rotation, mirror).  The transform of jitter j is a function of (seed, j) alone,

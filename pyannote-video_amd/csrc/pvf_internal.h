@@ -279,6 +279,7 @@ struct Ctx {
     size_t frame_pool_bytes = 0;
     void* ingest_rings = nullptr;                          // pinned staging rings of this context (ingest.hip)
     void* render_state = nullptr;                          // what the demo renderer keeps per context (render.hip)
+    void* tube_state = nullptr;                            // what pvf_frame_crops keeps per context (tube.hip)
     struct MlPlanCache* ml_plans = nullptr;   // detector launch plans of this context (detect.hip); freed by ml_plans_free
     std::map<std::vector<int>, std::unique_ptr<DevBuf>> resize_tabs;   // pvf_frame_resize coefficient tables by (in_w, in_h, out_w, out_h)
     const void* feat_ring_owner = nullptr;    // plan whose zero padding ring s_feat currently holds
@@ -376,6 +377,7 @@ void ingest_free_all(Ctx* c);
 struct ResizeTab { std::vector<int32_t> idx; std::vector<int16_t> coef; };
 ResizeTab linear_table(int in, int out);
 void render_free_all(Ctx* c);            // render.hip: resize tables, scratch and egress rings of the context
+void tube_free_all(Ctx* c);              // tube.hip: output buffers, copy stream and events of pvf_frame_crops
 void det_nms(const DetectorModel& m, const std::vector<RawDet>& sorted, std::vector<RawDet>& out);
 void det_pyramid_level(Ctx* c, const Frame& f, int upsample, int level, std::vector<uint8_t>* out, int* h, int* w);
 void det_level_features(Ctx* c, const Frame& f, int upsample, int level, std::vector<float>* out, int* fh, int* fw);

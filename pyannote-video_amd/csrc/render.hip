@@ -17,19 +17,6 @@
 
 static_assert(sizeof(pvf_prim) == 32, "pvf_prim is 8 x int32");
 
-// (yoff, Y row, U row, V row) of DEMO.md "Colour conversion": round(c * 65536), chroma rows summing to zero
-struct RenderCoef { int32_t yoff, y[3], u[3], v[3]; };
-static RenderCoef render_coef(int flags)
-{
-    static const RenderCoef tab[4] = {
-        {16, {16829, 33039, 6416}, {-9714, -19070, 28784}, {28784, -24103, -4681}},        // BT.601 limited
-        {16, {11966, 40254, 4064}, {-6596, -22188, 28784}, {28784, -26145, -2639}},        // BT.709 limited
-        {0, {19595, 38470, 7471}, {-11058, -21710, 32768}, {32768, -27439, -5329}},        // BT.601 full
-        {0, {13933, 46871, 4732}, {-7509, -25259, 32768}, {32768, -29763, -3005}},         // BT.709 full
-    };
-    return tab[(flags & PVF_YUV_BT709 ? 1 : 0) | (flags & PVF_YUV_FULL_RANGE ? 2 : 0)];
-}
-
 struct RenderArgs {
     const uint8_t* const* src;      // [n] resident RGB frames, ih x iw each
     int ih, iw, oh, ow;
@@ -87,8 +74,6 @@ __device__ __forceinline__ uint32_t redact_colour(const pvf_prim& p, const uint3
     }
     return out;
 }
-
-__device__ __forceinline__ int clip_shift(int v, int shift) { return min(max(v, 0), (256 << shift) - 1) >> shift; }      // clamp first (see yuv_clip8)
 
 // grid (ceil(ow / 32), ceil(oh / 32), n frames), 256 lanes: lane (tx, ty) owns output pixels (2 tx .. 2 tx + 1) x (2 ty .. 2 ty + 1) of the
 // tile.  Lanes of a wave cover 32 x 8 output pixels: their source reads fall into a few rows of the frame, their Y stores into 8 rows of
@@ -190,22 +175,20 @@ __global__ void __launch_bounds__(256) render_k(const RenderArgs a)
     const int cw = (a.ow + 1) >> 1, ch = (a.oh + 1) >> 1;
     uint8_t* up = yp + (size_t)a.oh * a.ow;
     uint8_t* vp = up + (size_t)cw * ch;
-    const int base16 = (a.k.yoff << 16) + 32768;
     int sr = 0, sg = 0, sb = 0;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-        const int y0v = clip_shift(a.k.y[0] * R[2 * j] + a.k.y[1] * G[2 * j] + a.k.y[2] * B[2 * j] + base16, 16);
-        const int y1v = clip_shift(a.k.y[0] * R[2 * j + 1] + a.k.y[1] * G[2 * j + 1] + a.k.y[2] * B[2 * j + 1] + base16, 16);
+        const int y0v = yuv_luma(a.k, R[2 * j], G[2 * j], B[2 * j]);
+        const int y1v = yuv_luma(a.k, R[2 * j + 1], G[2 * j + 1], B[2 * j + 1]);
         sr += R[2 * j] + R[2 * j + 1]; sg += G[2 * j] + G[2 * j + 1]; sb += B[2 * j] + B[2 * j + 1];
         if (j == 1 && !in_y1) continue;
         uint8_t* q = yp + (size_t)(Y0 + j) * a.ow + X0;
         if (in_x1 && ((uintptr_t)q & 1) == 0) *reinterpret_cast<uint16_t*>(q) = (uint16_t)(y0v | (y1v << 8));
         else { q[0] = (uint8_t)y0v; if (in_x1) q[1] = (uint8_t)y1v; }
     }
-    const int cbase = (128 << 18) + (1 << 17);
     const size_t ci = (size_t)(Y0 >> 1) * cw + (X0 >> 1);
-    up[ci] = (uint8_t)clip_shift(a.k.u[0] * sr + a.k.u[1] * sg + a.k.u[2] * sb + cbase, 18);
-    vp[ci] = (uint8_t)clip_shift(a.k.v[0] * sr + a.k.v[1] * sg + a.k.v[2] * sb + cbase, 18);
+    up[ci] = (uint8_t)yuv_chroma(a.k.u, sr, sg, sb);
+    vp[ci] = (uint8_t)yuv_chroma(a.k.v, sr, sg, sb);
 }
 
 // ---- the cell means of a call's redactions (REDACT.md "Cells") --------------------------------------------------------------------

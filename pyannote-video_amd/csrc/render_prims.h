@@ -65,3 +65,29 @@ __device__ __forceinline__ bool prim_covers(const pvf_prim& p, const uint8_t* __
     const int g = (ch >= 32 && ch <= 126) ? ch - 32 : '?' - 32;
     return (render_font[g][row] >> (4 - col)) & 1;
 }
+
+// ---- colour conversion (DEMO.md "Colour conversion"): what render.hip's render_k and tube.hip's crop_k turn a drawn RGB picture into
+// (yoff, Y row, U row, V row) of DEMO.md "Colour conversion": round(c * 65536), chroma rows summing to zero
+struct RenderCoef { int32_t yoff, y[3], u[3], v[3]; };
+static inline RenderCoef render_coef(int flags)
+{
+    static const RenderCoef tab[4] = {
+        {16, {16829, 33039, 6416}, {-9714, -19070, 28784}, {28784, -24103, -4681}},        // BT.601 limited
+        {16, {11966, 40254, 4064}, {-6596, -22188, 28784}, {28784, -26145, -2639}},        // BT.709 limited
+        {0, {19595, 38470, 7471}, {-11058, -21710, 32768}, {32768, -27439, -5329}},        // BT.601 full
+        {0, {13933, 46871, 4732}, {-7509, -25259, 32768}, {32768, -29763, -3005}},         // BT.709 full
+    };
+    return tab[(flags & PVF_YUV_BT709 ? 1 : 0) | (flags & PVF_YUV_FULL_RANGE ? 2 : 0)];
+}
+
+__device__ __forceinline__ int clip_shift(int v, int shift) { return min(max(v, 0), (256 << shift) - 1) >> shift; }      // clamp first (see yuv_clip8)
+// the luma of one pixel
+__device__ __forceinline__ int yuv_luma(const RenderCoef& k, int r, int g, int b)
+{
+    return clip_shift(k.y[0] * r + k.y[1] * g + k.y[2] * b + (k.yoff << 16) + 32768, 16);
+}
+// one chroma sample from the sums of its 2 x 2 pixels (a pixel past an odd picture's edge is its neighbour, counted again); row: k.u or k.v
+__device__ __forceinline__ int yuv_chroma(const int32_t (&row)[3], int sr, int sg, int sb)
+{
+    return clip_shift(row[0] * sr + row[1] * sg + row[2] * sb + (128 << 18) + (1 << 17), 18);
+}

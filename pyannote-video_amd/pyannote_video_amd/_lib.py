@@ -100,6 +100,8 @@ _SIGS = {
     # the talk verb (TALK.md): mouth motion of a face chip against the face before it
     "pvf_chip_motion": (C.c_int32, [H, P, C.c_int32, P, P]),
     "pvf_face_motion": (C.c_int32, [H, P, P, C.c_int32, P, P]),
+    # the tube verb (TUBE.md): square windows of resident frames as S x S pictures
+    "pvf_frame_crops": (C.c_int32, [H, P, P, C.c_int32, C.c_int32, C.c_int32, P, C.c_int32]),
     # num_jitters (JITTER.md): compute_face_descriptor(img, shape, num_jitters)
     "pvf_jitter_plan": (C.c_int32, [C.c_int32, C.c_uint64, P]),
     "pvf_debug_jitter_chips": (C.c_int32, [H, P, C.c_int32, C.c_int32, C.c_uint64, P]),

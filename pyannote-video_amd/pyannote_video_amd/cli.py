@@ -832,6 +832,141 @@ def talk(video, tracking, landmarks, output, window=0.4, on=3.0, off=1.5, min_du
     return {"faces": len(all_faces), "linked": int(sum(linked)), "segments": segs}
 
 
+def tube(video, tracking, landmarks, output, size=224, region="face", scale=None, smooth=0.5, label=None, only=None, segments=None,
+         min_length=0.0, t_from=0.0, t_until=None, fmt="y4m", matrix="601", full_range=False, index=None, fps=25.0, ctx=None, batch=2048,
+         ahead=96, max_open=None):
+    """A fixed-size face or mouth video for every track (TUBE.md).  One pass over the video, shaped like `talk`'s: a reader thread pushes
+    the frames that carry chosen faces through the pinned ingest ring, this thread asks for `batch` pictures per library call (the
+    windows are resampled, and for Y4M converted, on the device from the resident frames; only the pictures come back) and appends
+    each to the file of its tube.  The windows are made before the pass (tube.py), so every file's length is known when it is opened;
+    at most `max_open` files are open at a time (tube.FilePool).  Returns {"tubes", "pictures", "files", "open_peak"}."""
+    import os
+    import queue
+    import threading
+    from . import faces as _faces, pipeline, render, runtime, tube as _tube
+    ctx = ctx or runtime.default_context()
+    if fmt not in ("y4m", "npy"):
+        raise ValueError("tube: the format is y4m or npy")
+    if region == "mouth" and landmarks is None:
+        raise ValueError("tube: --region mouth needs the landmarks file of `extract` between the tracking file and the output directory")
+    if not _tube.MIN_SIZE <= int(size) <= _tube.MAX_SIZE:
+        raise ValueError("tube: --size is %d .. %d" % (_tube.MIN_SIZE, _tube.MAX_SIZE))
+    if int(batch) < 1 or int(batch) > _tube.MAX_CROPS:
+        raise ValueError("tube: a batch holds 1 .. %d pictures" % _tube.MAX_CROPS)
+    size = int(size)
+    frame_width, frame_height = video.frame_size
+    rows = formats.read_tracks(tracking) if isinstance(tracking, str) else tracking
+    labels = render.read_labels(label) if isinstance(label, str) else label
+    spans = _tube.read_segments(segments) if isinstance(segments, str) else segments
+    try:
+        n_frames = len(video)
+    except TypeError:                        # a stream: as many frame times as the tracking file needs
+        n_frames = int(max([r[0] for r in rows] or [0.0]) * video.frame_rate) + 2
+    times = [i / video.frame_rate for i in range(n_frames)]
+    if region == "mouth":
+        marks = formats.read_landmarks(landmarks) if isinstance(landmarks, str) else landmarks
+        all_faces = _faces.landmark_faces(rows, marks, times, frame_width, frame_height)
+    else:
+        all_faces = [(T, int(ident), fi, box, None) for fi, T, g in pipeline.faces_per_frame(rows, times, frame_width, frame_height, drop_last=False)
+                     for ident, box in g]
+    tubes = _tube.plan(all_faces, region, scale, smooth, labels, only, spans, min_length, t_from, t_until, fmt)
+    os.makedirs(output, exist_ok=True)
+    by_frame = {}                            # frame index -> [(tube, picture, window)]
+    for ti, (_, _, part) in enumerate(tubes):
+        for k, (i, _, win) in enumerate(part):
+            by_frame.setdefault(all_faces[i][2], []).append((ti, k, win))
+    pool = _tube.FilePool(_tube.MAX_OPEN if max_open is None else max_open)
+    writers, left = {}, [len(part) for _, _, part in tubes]
+    rate = render.rate_tag(video, fps)
+
+    def write(ti, picture):
+        if ti not in writers:
+            target = _tube.PooledFile(pool, os.path.join(output, tubes[ti][0]))
+            writers[ti] = (_tube.NpyWriter(target, left[ti], size) if fmt == "npy" else render.Y4mWriter(target, size, size, rate, full_range))
+        writers[ti].write(picture)
+        left[ti] -= 1
+        if not left[ti]:
+            writers.pop(ti).close()
+
+    last_wanted = max(by_frame) if by_frame else -1
+    q = queue.Queue(maxsize=max(2, int(ahead)))
+    state = {"error": None}
+
+    def reader():
+        stager = runtime.HostFrameStager(ctx, 16)
+        try:
+            if last_wanted >= 0:
+                for fi, (t, rgb) in enumerate(video):
+                    if fi > last_wanted or state["error"] is not None:
+                        break
+                    if fi not in by_frame:
+                        continue
+                    rgb, owned = stager.stage(rgb)
+                    q.put((fi, rgb, owned))
+            stager.close()
+        except BaseException as e:          # noqa: BLE001 -- re-raised below
+            state["error"] = e
+        finally:
+            q.put(None)
+
+    th = threading.Thread(target=reader, name="pvface-tube-reader")
+    th.start()
+    pend = []
+    try:
+        def flush():
+            frames, jobs = [], []
+            for fi, dev, _ in pend:
+                for job in by_frame[fi]:
+                    frames.append(dev); jobs.append(job)
+            for k0 in range(0, len(jobs), int(batch)):
+                part = jobs[k0:k0 + int(batch)]
+                got = ctx.frame_crops(frames[k0:k0 + int(batch)], [j[2] for j in part], size, "rgb" if fmt == "npy" else "yuv420", matrix, full_range)
+                for (ti, _, _), picture in zip(part, got):
+                    write(ti, picture)
+            for _, dev, owned in pend:
+                if owned:
+                    dev.release()
+            del pend[:]
+        while state["error"] is None:
+            item = q.get()
+            if item is None:
+                break
+            pend.append(item)
+            if sum(len(by_frame[fi]) for fi, _, _ in pend) >= batch:
+                flush()
+        if state["error"] is None and pend:
+            flush()
+    except BaseException as e:              # noqa: BLE001 -- re-raised below
+        state["error"] = state["error"] or e
+    finally:
+        while th.is_alive():                 # an error on this side: let the reader run out
+            try:
+                item = q.get(timeout=0.05)
+                if item is not None:
+                    pend.append(item)
+            except queue.Empty:
+                pass
+        th.join()
+        while not q.empty():
+            item = q.get()
+            if item is not None:
+                pend.append(item)
+        for _, dev, owned in pend:
+            if owned:
+                dev.release()
+        for wr in writers.values():
+            wr.close()
+        pool.close()
+    if state["error"] is not None:
+        raise state["error"]
+    if index:
+        with open(index, "w") as fx:
+            for fname, track, part in tubes:
+                for k, (_, T, win) in enumerate(part):
+                    fx.write(_tube.index_line(fname, k, T, track, win))
+    return {"tubes": len(tubes), "pictures": sum(len(part) for _, _, part in tubes), "files": [t[0] for t in tubes], "open_peak": pool.peak}
+
+
 def _names(text):
     return set(n for n in text.split(",") if n)
 
@@ -968,6 +1103,25 @@ def _parser():
     tk.add_argument("--until", dest="t_until", type=float, default=None, help="end, seconds (default: the video's duration)")
     tk.add_argument("--label", default=None, help="`identifier name` lines: --segments lines end in the track's name")
     tk.add_argument("--segments", default=None, help="write `track start end mean_s` per talking span")
+    tb = sub.add_parser("tube", help="a fixed-size face or mouth video for every track, as YUV4MPEG2 or .npy files in a directory")
+    tb.add_argument("video"); tb.add_argument("tracking")
+    tb.add_argument("rest", nargs="+", metavar="[landmarks] output-directory", help="landmarks.txt of `extract` (needed by --region mouth "
+                    "only), then the directory the tubes are written to")
+    tb.add_argument("--size", type=int, default=224, help="side of the pictures, 1 .. 1024")
+    tb.add_argument("--region", choices=("face", "mouth"), default="face")
+    tb.add_argument("--scale", type=float, default=None, help="face: the window's side over the larger side of the track box (default 1.6); "
+                    "mouth: over the same at scale 1 (default 0.5)")
+    tb.add_argument("--smooth", type=float, default=0.5, help="seconds the window's centre and side are averaged over (0: the raw values)")
+    tb.add_argument("--label", default=None, help="`identifier name` lines, what `cluster` and `identify` write")
+    tb.add_argument("--only", type=_names, default=None, metavar="A,B", help="only the tracks with these names (#7 or 7 for a track)")
+    tb.add_argument("--segments", default=None, help="the file `talk --segments` wrote: one tube per span, track_%%05d_%%03d")
+    tb.add_argument("--min-length", type=float, default=0.0, help="tubes shorter than this many seconds are dropped")
+    tb.add_argument("--from", dest="t_from", type=float, default=0.0, help="start, seconds")
+    tb.add_argument("--until", dest="t_until", type=float, default=None, help="end, seconds (default: the video's duration)")
+    tb.add_argument("--format", dest="fmt", choices=("y4m", "npy"), default="y4m")
+    tb.add_argument("--matrix", dest="out_matrix", choices=("601", "709"), default=None, help="YUV matrix of the Y4M tubes (default: the video's, else 601)")
+    tb.add_argument("--range", dest="out_range", choices=("limited", "full"), default=None, help="sample range of the Y4M tubes")
+    tb.add_argument("--index", default=None, help="write `file picture T track X0 Y0 L` per picture")
     return ap
 
 
@@ -990,7 +1144,7 @@ def main(argv=None):
         if a.video == "-" and a.verb == "faces":
             ap.error("faces reads the video twice, once for the quality of every face and once for the frames of the chosen ones: "
                      "give it a file, not a stream on stdin")
-        if a.video == "-" and a.verb not in ("track", "process", "talk"):
+        if a.video == "-" and a.verb not in ("track", "process", "talk", "tube"):
             ap.error("%s needs the length of the video: give it a file, not a stream on stdin" % a.verb)
         over = {}
         if a.matrix is not None:
@@ -1045,6 +1199,18 @@ def main(argv=None):
         try:
             res = talk(video(), a.tracking, a.landmarks, a.output, window=a.window, on=a.on, off=a.off, min_duration=a.min_duration,
                        max_pause=a.max_pause, max_dark=a.max_dark, t_from=a.t_from, t_until=a.t_until, label=a.label, segments=a.segments, ctx=ctx)
+        except (KeyError, ValueError) as e:
+            ap.error(str(e.args[0]) if e.args else str(e))
+    elif a.verb == "tube":
+        if len(a.rest) > 2:
+            ap.error("tube takes <video> <tracking> [<landmarks>] <output-directory>")
+        try:
+            v = video()
+            rng = a.out_range or a.range
+            res = tube(v, a.tracking, a.rest[0] if len(a.rest) == 2 else None, a.rest[-1], size=a.size, region=a.region, scale=a.scale,
+                       smooth=a.smooth, label=a.label, only=a.only, segments=a.segments, min_length=a.min_length, t_from=a.t_from,
+                       t_until=a.t_until, fmt=a.fmt, matrix=a.out_matrix or a.matrix or getattr(v, "matrix", "601"),
+                       full_range=(rng == "full") if rng is not None else bool(getattr(v, "full_range", False)), index=a.index, fps=a.fps, ctx=ctx)
         except (KeyError, ValueError) as e:
             ap.error(str(e.args[0]) if e.args else str(e))
     elif a.verb == "extract":

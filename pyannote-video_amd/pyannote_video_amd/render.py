@@ -356,8 +356,11 @@ class Y4mWriter(object):
     def __init__(self, target, width, height, rate="25:1", full_range=False):
         self.width, self.height = int(width), int(height)
         self.frame_bytes = self.width * self.height + 2 * ((self.width + 1) // 2) * ((self.height + 1) // 2)
-        self._own = target != "-"
-        self._f = open(target, "wb") if self._own else sys.stdout.buffer
+        if hasattr(target, "write"):             # an object to write to (tube.PooledFile): closed with the writer
+            self._own, self._f = True, target
+        else:
+            self._own = target != "-"
+            self._f = open(target, "wb") if self._own else sys.stdout.buffer
         self.frames = 0
         head = "YUV4MPEG2 W%d H%d F%s C420" % (self.width, self.height, rate)
         if full_range:

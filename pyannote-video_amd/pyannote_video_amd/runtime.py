@@ -781,6 +781,25 @@ class Context(object):
             check(self._l.pvf_face_motion(self._h, ptr(self._handles(frames)), ptr(pts), len(pts), ptr(prev), ptr(out)))
         return out
 
+    # ---- the tube verb (TUBE.md)
+    def frame_crops(self, frames, windows, size, layout="rgb", matrix="601", full_range=False, out_ptr=None):
+        """the windows (X0, Y0, L), in sixteenths of a pixel, of resident frames as size x size pictures (pvf_frame_crops): uint8
+        [n, size, size, 3] for layout "rgb", [n, picture bytes] (Y, U, V tight) for "yuv420".  With out_ptr, a device address that holds
+        as much, the pictures stay in HBM and nothing is returned."""
+        if str(layout) not in ("rgb", "yuv420"):
+            raise ValueError("layout must be 'rgb' or 'yuv420', not %r" % (layout,))
+        windows = np.ascontiguousarray(windows, np.int32).reshape(-1, 3)
+        n, size = len(windows), int(size)
+        if len(frames) != n:
+            raise ValueError("frame_crops: one frame per window")
+        flags = _yuv_flags(matrix, full_range) | (4 if layout == "yuv420" else 0)      # PVF_CROP_YUV420
+        shape = (n, size, size, 3) if layout == "rgb" else (n, size * size + 2 * ((size + 1) // 2) ** 2)
+        out = None if out_ptr is not None else np.empty(shape if size > 0 else (n, 0), np.uint8)
+        with self._staging():
+            check(self._l.pvf_frame_crops(self._h, ptr(self._handles(frames)), ptr(windows), n, size, flags,
+                                          C.c_void_p(int(out_ptr)) if out_ptr is not None else ptr(out), 1 if out_ptr is not None else 0))
+        return out
+
     @staticmethod
     def _sheet_args(n, xy, background, prims):
         from . import render as _render
