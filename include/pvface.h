@@ -336,6 +336,19 @@ int32_t pvf_face_motion(pvf_handle ctx, const pvf_handle* frames, const int32_t*
 int32_t pvf_frame_crops(pvf_handle ctx, const pvf_handle* frames, const int32_t* windows /* n*3 */, int32_t n, int32_t S, int32_t flags,
                         uint8_t* out, int32_t out_on_device);
 
+/* ---- tube --align: oriented windows (TUBE.md "Oriented window"; no reference call) ------------------------------- */
+#define PVF_WARP_MAX_K 16                /* sub-samples per output pixel and axis: K^2 x 65536 x 255.5 < 2^32, a pixel's sum is 32-bit */
+#define PVF_WARP_MAX_STEP (1 << 20)      /* |BX|, |BY| in 1/65536 pixel: a sub-step of 16 pixels, from where aliasing is accepted */
+/* n pictures of S x S pixels as pvf_frame_crops returns them (layouts, flags, rounds, where out lies, n = 0), through windows that
+ * need not be axis-aligned: picture i is the window windows[5 i .. 5 i + 4] = (CX, CY, BX, BY, K) of frame frames[i].  (CX, CY): the
+ * centre in sixteenths of a source pixel; (BX, BY): the step between sub-samples along an output row in 1/65536 pixel, (-BY, BX) down
+ * a column; K x K sub-samples, bilinear with 8-bit fractions, make an output pixel:
+ * (sum of their four weighted taps + 32768 K^2) // (65536 K^2); outside the frame reads black.  TUBE.md states the positions; integer
+ * arithmetic throughout.  (0, 0) is a valid step.  Refused before any work for pvf_frame_crops' reasons (S, n, |CX|, |CY| <=
+ * PVF_CROP_MAX_COORD, flags, pointers, frames) and for K outside 1 .. PVF_WARP_MAX_K or |BX|, |BY| beyond PVF_WARP_MAX_STEP. */
+int32_t pvf_frame_warps(pvf_handle ctx, const pvf_handle* frames, const int32_t* windows /* n*5 */, int32_t n, int32_t S, int32_t flags,
+                        uint8_t* out, int32_t out_on_device);
+
 /* ---- num_jitters (JITTER.md) ------------------------------------------------------------------------
  * dlib: compute_face_descriptor(img, shape, num_jitters) -- the descriptor is the fp32 mean of the network's outputs on J = num_jitters
  * perturbed copies of the aligned chip (shift, zoom, rotation, mirror).  The transform of jitter j is a function of (seed, j) alone,

@@ -5,6 +5,10 @@
 //            to the 64-bit sums of the output row being made and of the one below it (a source row lies in at most two output rows when
 //            reducing).  A finished row is divided by its exact quotient and leaves as RGB bytes or, converted with render_k's own
 //            device code (render_prims.h), as planar YUV 4:2:0 -- a lane pair and two consecutive rows of a band make a chroma sample.
+//   warp_k   the oriented window of `tube --align` (TUBE.md "Oriented window"): a block per (crop, W_SIDE x W_SIDE tile of output pixels), a
+//            lane per output pixel.  The block bounds the source pixels its K x K sub-samples per pixel can touch from the tile's four
+//            corner sub-samples, stages that box in LDS through crop_k's descriptor when it fits W_TILE bytes and takes its taps through
+//            the descriptor one by one when it does not; a lane then sums its K^2 bilinear sub-samples in 32 bits.
 // The two regimes of TUBE.md (area average at L >= 16 S, bilinear below) are the same separable weighted sum with other weights and
 // another divisor, so they are one kernel; a block takes the regime of its crop.  Every sum is an integer sum: neither the pieces, the
 // bands, the LDS tiles nor the rounds of a call change a bit (tests/tube_ref.py restates the arithmetic; the kernel is held to it).
@@ -198,6 +202,133 @@ __global__ void __launch_bounds__(C_COLS) crop_k(const CropArgs a)
     for (; r < r1; ++r) finish(r);
 }
 
+
+// ---- the oriented window ---------------------------------------------------------------------------------------------------------------
+constexpr int W_SIDE = 16;          // output pixels of a tile along each axis, a lane each (even: a 2 x 2 chroma sample never leaves a block)
+constexpr int W_TILE = 24576;       // LDS bytes of a staged box: 6 blocks of 4 waves a CU (24 of its 32 waves, 144 of its 160 KiB).  A 16-pixel
+                                    // tile of a face at 3.5 : 1, rolled 30 degrees, touches 78 x 78 source pixels: 19 KiB.  A larger box
+                                    // goes to the direct path.
+static_assert(W_SIDE % 2 == 0 && W_SIDE * W_SIDE % 64 == 0 && 64 % W_SIDE == 0, "a chroma sample's four lanes lie in one wave");
+// the bounds TUBE.md "Oriented window" argues from: which quantities need 64 bits and which fit 32
+static_assert((int64_t)8192 * PVF_CROP_MAX_COORD + (int64_t)2 * PVF_WARP_MAX_K * PVF_CROP_MAX_SIZE * PVF_WARP_MAX_STEP + 65536 >= ((int64_t)1 << 31),
+              "PX and PY of a sub-sample are 64-bit");
+static_assert((((int64_t)8192 * PVF_CROP_MAX_COORD + (int64_t)2 * PVF_WARP_MAX_K * PVF_CROP_MAX_SIZE * PVF_WARP_MAX_STEP + 65536) >> 17) + 1 < ((int64_t)1 << 30),
+              "source indices fit int32");
+static_assert(131071 + (int64_t)2 * 2 * W_SIDE * PVF_WARP_MAX_K * PVF_WARP_MAX_STEP < ((int64_t)1 << 31), "a sub-sample's position relative to its tile's first fits int32");
+static_assert((uint64_t)65536 * PVF_WARP_MAX_K * PVF_WARP_MAX_K * 255 + (uint64_t)32768 * PVF_WARP_MAX_K * PVF_WARP_MAX_K < ((uint64_t)1 << 32),
+              "a pixel's sum with its rounding term fits uint32");
+static_assert((255 * 2 + 1) * PVF_WARP_MAX_K * PVF_WARP_MAX_K / 2 < 65536 && PVF_WARP_MAX_K * PVF_WARP_MAX_K <= 256, "the quotient's numerator is below 2^16, its divisor at most 256");
+
+struct WarpJob { const uint8_t* img; int32_t h, w, CX, CY, BX, BY, K; uint32_t M; int32_t pad[2]; };      // M = 2^24 / K^2 + 1 (warp_quotient)
+static_assert(sizeof(WarpJob) == 48, "WarpJob is three 16-byte units");
+struct WarpArgs { const WarpJob* jobs; uint8_t* out; int S, yuv; RenderCoef k; };
+
+// v / d for v < 2^16, d <= 256 with M = 2^24 / d + 1: v M / 2^24 = v / d + v e / (d 2^24) with e = M d - 2^24 in 1 .. d, and v e < 2^24, so
+// the excess is below 1 / d, the least distance from v / d to the next integer (tests/csrc/warp_quotient_check.c runs every d and v)
+__host__ __device__ __forceinline__ uint32_t warp_quotient(uint32_t v, uint32_t M) { return (uint32_t)(((uint64_t)v * M) >> 24); }
+
+// grid (tiles across * tiles down, crops of the round), W_SIDE * W_SIDE lanes.
+// Units: 1 / 131072 pixel.  O = (OX, OY), 64-bit, is the position of the tile's first sub-sample; split as 2^17 (O >> 17) + (O & 131071) it
+// leaves every other sub-sample of the tile at a small int32 offset (static_assert above), and floor() is the arithmetic shift alone.
+__global__ void __launch_bounds__(W_SIDE * W_SIDE) warp_k(const WarpArgs a)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t s_tile[W_TILE];
+    const int tid = threadIdx.x, S = a.S;
+    const int across = (S + W_SIDE - 1) / W_SIDE;
+    const int j0 = (int)(blockIdx.x % across) * W_SIDE, i0 = (int)(blockIdx.x / across) * W_SIDE;
+    const int4* jq = reinterpret_cast<const int4*>(a.jobs + blockIdx.y);
+    const int4 q0 = jq[0], q1 = jq[1], q2 = jq[2];
+    const uint8_t* img = reinterpret_cast<const uint8_t*>(((uint64_t)(uint32_t)q0.y << 32) | (uint32_t)q0.x);
+    const int h = q0.z, w = q0.w, CX = q1.x, CY = q1.y, BX = q1.z, BY = q1.w, K = q2.x;
+    const uint32_t M = (uint32_t)q2.y;
+    const int tw = min(W_SIDE, S - j0), th = min(W_SIDE, S - i0);   // the tile's pixels inside the picture
+    const int64_t m0 = 2 * (int64_t)j0 * K + 1 - (int64_t)S * K, n0 = 2 * (int64_t)i0 * K + 1 - (int64_t)S * K;
+    const int64_t OX = (int64_t)8192 * CX + m0 * BX - n0 * BY - 65536, OY = (int64_t)8192 * CY + m0 * BY + n0 * BX - 65536;
+    const int ox = (int)(OX >> 17), oy = (int)(OY >> 17), rx = (int)(OX & 131071), ry = (int)(OY & 131071);
+
+    // the source pixels the tile can touch: a sub-sample's position is affine in (dm, dn), so its first tap is least and greatest at a corner
+    const int dmx = 2 * (tw * K - 1), dnx = 2 * (th * K - 1);
+    int bx0, bx1, by0, by1;
+    {
+        const int xa = rx, xb = rx + dmx * BX, xc = rx - dnx * BY, xd = rx + dmx * BX - dnx * BY;
+        const int ya = ry, yb = ry + dmx * BY, yc = ry + dnx * BX, yd = ry + dmx * BY + dnx * BX;
+        bx0 = max(ox + (min(min(xa, xb), min(xc, xd)) >> 17), 0); bx1 = min(ox + (max(max(xa, xb), max(xc, xd)) >> 17) + 1, w - 1);
+        by0 = max(oy + (min(min(ya, yb), min(yc, yd)) >> 17), 0); by1 = min(oy + (max(max(ya, yb), max(yc, yd)) >> 17) + 1, h - 1);
+    }
+    const bool any = bx0 <= bx1 && by0 <= by1;                      // else everything the tile sees is black: no loads
+    const int bw = bx1 - bx0 + 1, bh = by1 - by0 + 1;
+    const int pitch = any ? (3 + 3 * bw + 15) & ~15 : 16, n16 = pitch >> 4;
+    const bool staged = any && (int64_t)bh * pitch <= W_TILE;
+
+    // crop_k's descriptor: the base aligned down to 4 bytes, the range rounded up to whole dwords
+    const unsigned delta = (unsigned)((uintptr_t)img & 3u), rb = 3u * (unsigned)w;
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)((uintptr_t)img - delta), 0, (int)((delta + (unsigned)h * rb + 3u) & ~3u), 0x00020000);
+    if (staged) {
+        for (int u = tid; u < bh * n16; u += W_SIDE * W_SIDE) {     // (bh * n16 <= W_TILE / 16)
+            const int i = u / n16, k = u - i * n16;
+            const unsigned off = ((delta + (unsigned)(by0 + i) * rb + 3u * (unsigned)bx0) & ~3u) + 16u * (unsigned)k;
+            reinterpret_cast<uint4*>(s_tile)[u] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)off, 0, 0));
+        }
+    }
+    __syncthreads();
+
+    const int tx = tid % W_SIDE, ty = tid / W_SIDE, j = j0 + tx, i = i0 + ty;
+    const bool live = tx < tw && ty < th;
+    uint32_t sum[3] = {0, 0, 0};
+    if (live && any) {
+        // one tap: a pixel outside the box is outside the frame, or no sub-sample of the tile reaches it; it reads black, its weight counted
+        auto tap = [&](int x, int y, uint32_t wgt) {
+            if (x < bx0 || x > bx1 || y < by0 || y > by1 || wgt == 0) return;
+            const unsigned at = delta + (unsigned)y * rb + 3u * (unsigned)x;
+            if (staged) {
+                const uint8_t* s = s_tile + (y - by0) * pitch + (int)((delta + (unsigned)y * rb + 3u * (unsigned)bx0) & 3u) + 3 * (x - bx0);
+                sum[0] += wgt * s[0]; sum[1] += wgt * s[1]; sum[2] += wgt * s[2];
+            } else {
+                sum[0] += wgt * (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rs, (int)at, 0, 0);
+                sum[1] += wgt * (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rs, (int)at + 1, 0, 0);
+                sum[2] += wgt * (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rs, (int)at + 2, 0, 0);
+            }
+        };
+        const int px = rx + 2 * tx * K * BX - 2 * ty * K * BY, py = ry + 2 * tx * K * BY + 2 * ty * K * BX;       // sub-sample (0, 0) of this pixel
+        for (int b = 0; b < K; ++b) {
+            int sx = px - 2 * b * BY, sy = py + 2 * b * BX;
+            for (int c = 0; c < K; ++c, sx += 2 * BX, sy += 2 * BY) {
+                const int x0 = ox + (sx >> 17), y0 = oy + (sy >> 17);
+                const uint32_t fx = (uint32_t)(sx & 131071) >> 9, fy = (uint32_t)(sy & 131071) >> 9;
+                tap(x0, y0, (256u - fx) * (256u - fy)); tap(x0 + 1, y0, fx * (256u - fy));
+                tap(x0, y0 + 1, (256u - fx) * fy); tap(x0 + 1, y0 + 1, fx * fy);
+            }
+        }
+    }
+    int v[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = (int)warp_quotient((sum[c] + 32768u * (uint32_t)(K * K)) >> 16, M);
+
+    const int cw = (S + 1) >> 1;
+    const size_t crop_bytes = a.yuv ? (size_t)S * S + 2 * (size_t)cw * cw : (size_t)S * S * 3;
+    uint8_t* out = a.out + (size_t)blockIdx.y * crop_bytes;
+    if (!a.yuv) {
+        if (live) { uint8_t* o = out + ((size_t)i * S + j) * 3; o[0] = (uint8_t)v[0]; o[1] = (uint8_t)v[1]; o[2] = (uint8_t)v[2]; }
+        return;
+    }
+    if (live) out[(size_t)i * S + j] = (uint8_t)yuv_luma(a.k, v[0], v[1], v[2]);
+    // chroma: the lane to the right (tid ^ 1) and the pair below (tid ^ W_SIDE) lie in this wave; a pixel past an odd picture's edge is its
+    // neighbour counted again, as crop_k counts it
+    int quad[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const int right = __shfl_xor(v[c], 1);
+        const int pair = v[c] + (j + 1 < S ? right : v[c]);
+        const int below = __shfl_xor(pair, W_SIDE);
+        quad[c] = pair + (i + 1 < S ? below : pair);
+    }
+    if (live && !(i & 1) && !(j & 1)) {
+        uint8_t* up = out + (size_t)S * S + (size_t)(i >> 1) * cw + (j >> 1);
+        up[0] = (uint8_t)yuv_chroma(a.k.u, quad[0], quad[1], quad[2]);
+        up[(size_t)cw * cw] = (uint8_t)yuv_chroma(a.k.v, quad[0], quad[1], quad[2]);
+    }
+}
+
 // ---- the call ------------------------------------------------------------------------------------------------------------------------
 // what the context keeps for pvf_frame_crops: the two output buffers of the rounds, the job table, a copy stream and the events that
 // order a round's copy behind its kernel and the kernel after next behind the copy
@@ -243,6 +374,50 @@ static int crops_per_round(size_t crop_bytes)
     return std::min(m, C_ROUND_MAX);
 }
 
+static size_t picture_bytes(int S, bool yuv)
+{
+    const int cw = (S + 1) / 2;
+    return yuv ? (size_t)S * S + 2 * (size_t)cw * cw : (size_t)S * S * 3;
+}
+
+// The rounds of a call, shared by pvf_frame_crops and pvf_frame_warps: the n jobs (in the staging arena) go to the device, then
+// launch(jobs of the round on the device, their number, where their pictures go) is called once per round.
+template <typename Job, typename Launch>
+static void rounds_run(Ctx* c, TubeState& ts, const Job* jobs, int n, size_t crop_bytes, uint8_t* out, bool on_device, Launch launch)
+{
+    const int round = crops_per_round(crop_bytes);
+    ScratchLayout jl, ol;
+    const auto sJobs = jl.take<Job>((size_t)n);
+    const auto sOut = ol.take<uint8_t>((size_t)std::min(n, round) * crop_bytes);
+    ts.jobs.ensure(jl.bytes());
+    HIP_CHECK(hipMemcpyAsync(sJobs.in(ts.jobs), jobs, sJobs.bytes(), hipMemcpyHostToDevice, c->stream));
+    c->stage.sent(c->stream);
+    if (!on_device) { ts.out[0].ensure(ol.bytes()); if (n > round) ts.out[1].ensure(ol.bytes()); }
+    // round k's kernel writes buffer k & 1 on the context's stream; its copy to the host runs on the copy stream behind the kernel's event,
+    // while round k + 1's kernel, launched before the copy is asked for, runs; round k + 2's kernel waits for the copy's event
+    int k = 0, prev_i0 = -1, prev_m = 0;
+    auto copy_out = [&](int slot, int i0, int m) {
+        HIP_CHECK(hipStreamWaitEvent(ts.copy, ts.made[slot], 0));
+        HIP_CHECK(hipMemcpyAsync(out + (size_t)i0 * crop_bytes, sOut.in(ts.out[slot]), (size_t)m * crop_bytes, hipMemcpyDeviceToHost, ts.copy));
+        HIP_CHECK(hipEventRecord(ts.copied[slot], ts.copy));
+    };
+    for (int i0 = 0; i0 < n; i0 += round, ++k) {
+        const int m = std::min(round, n - i0), slot = k & 1;
+        if (!on_device && k >= 2) HIP_CHECK(hipStreamWaitEvent(c->stream, ts.copied[slot], 0));
+        {
+            ProfScope prof(c, "tube");
+            launch(sJobs.in(ts.jobs) + i0, m, on_device ? out + (size_t)i0 * crop_bytes : sOut.in(ts.out[slot]));
+            HIP_CHECK(hipGetLastError());
+        }
+        if (on_device) continue;
+        HIP_CHECK(hipEventRecord(ts.made[slot], c->stream));
+        if (prev_i0 >= 0) copy_out(slot ^ 1, prev_i0, prev_m);
+        prev_i0 = i0; prev_m = m;
+    }
+    if (!on_device) { copy_out((k - 1) & 1, prev_i0, prev_m); HIP_CHECK(hipStreamSynchronize(ts.copy)); }
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+}
+
 static void crops_run(Ctx* c, const pvf_handle* frames, const int32_t* windows, int n, int S, int flags, uint8_t* out, bool on_device)
 {
     const std::string w("pvf_frame_crops");
@@ -265,43 +440,45 @@ static void crops_run(Ctx* c, const pvf_handle* frames, const int32_t* windows, 
         jobs[i] = CropJob{f.d, f.h, f.w, windows[3 * i], windows[3 * i + 1], windows[3 * i + 2], 0};
     }
     const bool yuv = flags & PVF_CROP_YUV420;
-    const int cw = (S + 1) / 2;
-    const size_t crop_bytes = yuv ? (size_t)S * S + 2 * (size_t)cw * cw : (size_t)S * S * 3;
-    const int round = crops_per_round(crop_bytes);
-    ScratchLayout jl, ol;
-    const auto sJobs = jl.take<CropJob>((size_t)n);
-    const auto sOut = ol.take<uint8_t>((size_t)std::min(n, round) * crop_bytes);
-    ts.jobs.ensure(jl.bytes());
-    HIP_CHECK(hipMemcpyAsync(sJobs.in(ts.jobs), jobs, sJobs.bytes(), hipMemcpyHostToDevice, c->stream));
-    c->stage.sent(c->stream);
-    if (!on_device) { ts.out[0].ensure(ol.bytes()); if (n > round) ts.out[1].ensure(ol.bytes()); }
     const int pieces = (S + C_COLS - 1) / C_COLS, bands = (S + C_BAND - 1) / C_BAND;
     CropArgs a{nullptr, nullptr, S, yuv ? 1 : 0, render_coef(flags)};
-    // round k's kernel writes buffer k & 1 on the context's stream; its copy to the host runs on the copy stream behind the kernel's event,
-    // while round k + 1's kernel, launched before the copy is asked for, runs; round k + 2's kernel waits for the copy's event
-    int k = 0, prev_i0 = -1, prev_m = 0;
-    auto copy_out = [&](int slot, int i0, int m) {
-        HIP_CHECK(hipStreamWaitEvent(ts.copy, ts.made[slot], 0));
-        HIP_CHECK(hipMemcpyAsync(out + (size_t)i0 * crop_bytes, sOut.in(ts.out[slot]), (size_t)m * crop_bytes, hipMemcpyDeviceToHost, ts.copy));
-        HIP_CHECK(hipEventRecord(ts.copied[slot], ts.copy));
-    };
-    for (int i0 = 0; i0 < n; i0 += round, ++k) {
-        const int m = std::min(round, n - i0), slot = k & 1;
-        a.jobs = sJobs.in(ts.jobs) + i0;
-        a.out = on_device ? out + (size_t)i0 * crop_bytes : sOut.in(ts.out[slot]);
-        if (!on_device && k >= 2) HIP_CHECK(hipStreamWaitEvent(c->stream, ts.copied[slot], 0));
-        {
-            ProfScope prof(c, "tube");
-            hipLaunchKernelGGL(crop_k, dim3((unsigned)(pieces * bands), (unsigned)m), dim3(C_COLS), 0, c->stream, a);
-            HIP_CHECK(hipGetLastError());
-        }
-        if (on_device) continue;
-        HIP_CHECK(hipEventRecord(ts.made[slot], c->stream));
-        if (prev_i0 >= 0) copy_out(slot ^ 1, prev_i0, prev_m);
-        prev_i0 = i0; prev_m = m;
+    rounds_run(c, ts, jobs, n, picture_bytes(S, yuv), out, on_device, [&](const CropJob* dev_jobs, int m, uint8_t* dst) {
+        a.jobs = dev_jobs; a.out = dst;
+        hipLaunchKernelGGL(crop_k, dim3((unsigned)(pieces * bands), (unsigned)m), dim3(C_COLS), 0, c->stream, a);
+    });
+}
+
+static void warps_run(Ctx* c, const pvf_handle* frames, const int32_t* windows, int n, int S, int flags, uint8_t* out, bool on_device)
+{
+    const std::string w("pvf_frame_warps");
+    PVF_REQUIRE(n >= 0 && n <= PVF_CROP_MAX_CROPS, w + ": n outside 0 .. PVF_CROP_MAX_CROPS");
+    if (n == 0) return;
+    PVF_REQUIRE(frames && windows && out, w + ": null frames, windows or output");
+    PVF_REQUIRE(S >= PVF_CROP_MIN_SIZE && S <= PVF_CROP_MAX_SIZE, w + ": S outside PVF_CROP_MIN_SIZE .. PVF_CROP_MAX_SIZE");
+    PVF_REQUIRE((flags & ~(PVF_CROP_YUV420 | PVF_YUV_BT709 | PVF_YUV_FULL_RANGE)) == 0, w + ": unknown flags");
+    for (int i = 0; i < n; ++i) {                // nothing the kernel computes with is taken on trust
+        const int32_t* q = windows + (size_t)5 * i;
+        PVF_REQUIRE(q[4] >= 1 && q[4] <= PVF_WARP_MAX_K, w + ": K outside 1 .. PVF_WARP_MAX_K");
+        PVF_REQUIRE(q[2] >= -PVF_WARP_MAX_STEP && q[2] <= PVF_WARP_MAX_STEP && q[3] >= -PVF_WARP_MAX_STEP && q[3] <= PVF_WARP_MAX_STEP,
+                    w + ": BX or BY beyond PVF_WARP_MAX_STEP");
+        PVF_REQUIRE(q[0] >= -PVF_CROP_MAX_COORD && q[0] <= PVF_CROP_MAX_COORD && q[1] >= -PVF_CROP_MAX_COORD && q[1] <= PVF_CROP_MAX_COORD,
+                    w + ": CX or CY beyond PVF_CROP_MAX_COORD");
     }
-    if (!on_device) { copy_out((k - 1) & 1, prev_i0, prev_m); HIP_CHECK(hipStreamSynchronize(ts.copy)); }
-    HIP_CHECK(hipStreamSynchronize(c->stream));
+    TubeState& ts = tstate(c);
+    WarpJob* jobs = reinterpret_cast<WarpJob*>(c->stage.take((size_t)n * sizeof(WarpJob)));
+    for (int i = 0; i < n; ++i) {
+        const Frame f = c->frame(frames[i]);
+        PVF_REQUIRE(f.h >= 1 && f.w >= 1 && (int64_t)f.h * f.w * 3 + 6 < ((int64_t)1 << 31), w + ": a frame of 2 GiB or more");
+        const int32_t* q = windows + (size_t)5 * i;
+        jobs[i] = WarpJob{f.d, f.h, f.w, q[0], q[1], q[2], q[3], q[4], ((uint32_t)1 << 24) / (uint32_t)(q[4] * q[4]) + 1u, {0, 0}};
+    }
+    const bool yuv = flags & PVF_CROP_YUV420;
+    const int tiles = (S + W_SIDE - 1) / W_SIDE;
+    WarpArgs a{nullptr, nullptr, S, yuv ? 1 : 0, render_coef(flags)};
+    rounds_run(c, ts, jobs, n, picture_bytes(S, yuv), out, on_device, [&](const WarpJob* dev_jobs, int m, uint8_t* dst) {
+        a.jobs = dev_jobs; a.out = dst;
+        hipLaunchKernelGGL(warp_k, dim3((unsigned)(tiles * tiles), (unsigned)m), dim3(W_SIDE * W_SIDE), 0, c->stream, a);
+    });
 }
 
 #define API_BEGIN try {
@@ -319,5 +496,16 @@ extern "C" int32_t pvf_frame_crops(pvf_handle h, const pvf_handle* frames, const
     std::lock_guard<std::recursive_mutex> _api_lock(c->api_mu);
     HIP_CHECK(hipSetDevice(c->device));
     crops_run(c, frames, windows, n, S, flags, out, out_on_device != 0);
+    API_END
+}
+
+extern "C" int32_t pvf_frame_warps(pvf_handle h, const pvf_handle* frames, const int32_t* windows, int32_t n, int32_t S, int32_t flags, uint8_t* out,
+                                   int32_t out_on_device)
+{
+    API_BEGIN
+    Ctx* c = pvf_ctx(h);
+    std::lock_guard<std::recursive_mutex> _api_lock(c->api_mu);
+    HIP_CHECK(hipSetDevice(c->device));
+    warps_run(c, frames, windows, n, S, flags, out, out_on_device != 0);
     API_END
 }

@@ -102,6 +102,8 @@ _SIGS = {
     "pvf_face_motion": (C.c_int32, [H, P, P, C.c_int32, P, P]),
     # the tube verb (TUBE.md): square windows of resident frames as S x S pictures
     "pvf_frame_crops": (C.c_int32, [H, P, P, C.c_int32, C.c_int32, C.c_int32, P, C.c_int32]),
+    # tube --align: oriented windows (CX, CY, BX, BY, K) of resident frames as S x S pictures
+    "pvf_frame_warps": (C.c_int32, [H, P, P, C.c_int32, C.c_int32, C.c_int32, P, C.c_int32]),
     # num_jitters (JITTER.md): compute_face_descriptor(img, shape, num_jitters)
     "pvf_jitter_plan": (C.c_int32, [C.c_int32, C.c_uint64, P]),
     "pvf_debug_jitter_chips": (C.c_int32, [H, P, C.c_int32, C.c_int32, C.c_uint64, P]),

@@ -834,12 +834,13 @@ def talk(video, tracking, landmarks, output, window=0.4, on=3.0, off=1.5, min_du
 
 def tube(video, tracking, landmarks, output, size=224, region="face", scale=None, smooth=0.5, label=None, only=None, segments=None,
          min_length=0.0, t_from=0.0, t_until=None, fmt="y4m", matrix="601", full_range=False, index=None, fps=25.0, ctx=None, batch=2048,
-         ahead=96, max_open=None):
+         ahead=96, max_open=None, align=False):
     """A fixed-size face or mouth video for every track (TUBE.md).  One pass over the video, shaped like `talk`'s: a reader thread pushes
     the frames that carry chosen faces through the pinned ingest ring, this thread asks for `batch` pictures per library call (the
     windows are resampled, and for Y4M converted, on the device from the resident frames; only the pictures come back) and appends
     each to the file of its tube.  The windows are made before the pass (tube.py), so every file's length is known when it is opened;
-    at most `max_open` files are open at a time (tube.FilePool).  Returns {"tubes", "pictures", "files", "open_peak"}."""
+    at most `max_open` files are open at a time (tube.FilePool).  With `align` the windows follow the smoothed eye line of the landmarks
+    (oriented windows, Context.frame_warps) and the index lines carry `CX CY BX BY K`.  Returns {"tubes", "pictures", "files", "open_peak"}."""
     import os
     import queue
     import threading
@@ -849,6 +850,8 @@ def tube(video, tracking, landmarks, output, size=224, region="face", scale=None
         raise ValueError("tube: the format is y4m or npy")
     if region == "mouth" and landmarks is None:
         raise ValueError("tube: --region mouth needs the landmarks file of `extract` between the tracking file and the output directory")
+    if align and landmarks is None:
+        raise ValueError("tube: --align needs the landmarks file of `extract` between the tracking file and the output directory")
     if not _tube.MIN_SIZE <= int(size) <= _tube.MAX_SIZE:
         raise ValueError("tube: --size is %d .. %d" % (_tube.MIN_SIZE, _tube.MAX_SIZE))
     if int(batch) < 1 or int(batch) > _tube.MAX_CROPS:
@@ -863,13 +866,14 @@ def tube(video, tracking, landmarks, output, size=224, region="face", scale=None
     except TypeError:                        # a stream: as many frame times as the tracking file needs
         n_frames = int(max([r[0] for r in rows] or [0.0]) * video.frame_rate) + 2
     times = [i / video.frame_rate for i in range(n_frames)]
-    if region == "mouth":
+    if region == "mouth" or align:
         marks = formats.read_landmarks(landmarks) if isinstance(landmarks, str) else landmarks
         all_faces = _faces.landmark_faces(rows, marks, times, frame_width, frame_height)
-    else:
-        all_faces = [(T, int(ident), fi, box, None) for fi, T, g in pipeline.faces_per_frame(rows, times, frame_width, frame_height, drop_last=False)
-                     for ident, box in g]
-    tubes = _tube.plan(all_faces, region, scale, smooth, labels, only, spans, min_length, t_from, t_until, fmt)
+    if region == "face":                     # every face of the tracking file; aligned, with its points where the landmark file has a row for it
+        points = dict(((int(round(f[0] * 1000.0)), f[1]), f[4]) for f in all_faces) if align else {}
+        all_faces = [(T, int(ident), fi, box, points.get((int(round(T * 1000.0)), int(ident))))
+                     for fi, T, g in pipeline.faces_per_frame(rows, times, frame_width, frame_height, drop_last=False) for ident, box in g]
+    tubes = _tube.plan(all_faces, region, scale, smooth, labels, only, spans, min_length, t_from, t_until, fmt, align=bool(align), size=size)
     os.makedirs(output, exist_ok=True)
     by_frame = {}                            # frame index -> [(tube, picture, window)]
     for ti, (_, _, part) in enumerate(tubes):
@@ -920,7 +924,7 @@ def tube(video, tracking, landmarks, output, size=224, region="face", scale=None
                     frames.append(dev); jobs.append(job)
             for k0 in range(0, len(jobs), int(batch)):
                 part = jobs[k0:k0 + int(batch)]
-                got = ctx.frame_crops(frames[k0:k0 + int(batch)], [j[2] for j in part], size, "rgb" if fmt == "npy" else "yuv420", matrix, full_range)
+                got = (ctx.frame_warps if align else ctx.frame_crops)(frames[k0:k0 + int(batch)], [j[2] for j in part], size, "rgb" if fmt == "npy" else "yuv420", matrix, full_range)
                 for (ti, _, _), picture in zip(part, got):
                     write(ti, picture)
             for _, dev, owned in pend:
@@ -1106,7 +1110,7 @@ def _parser():
     tb = sub.add_parser("tube", help="a fixed-size face or mouth video for every track, as YUV4MPEG2 or .npy files in a directory")
     tb.add_argument("video"); tb.add_argument("tracking")
     tb.add_argument("rest", nargs="+", metavar="[landmarks] output-directory", help="landmarks.txt of `extract` (needed by --region mouth "
-                    "only), then the directory the tubes are written to")
+                    "and by --align), then the directory the tubes are written to")
     tb.add_argument("--size", type=int, default=224, help="side of the pictures, 1 .. 1024")
     tb.add_argument("--region", choices=("face", "mouth"), default="face")
     tb.add_argument("--scale", type=float, default=None, help="face: the window's side over the larger side of the track box (default 1.6); "
@@ -1121,7 +1125,9 @@ def _parser():
     tb.add_argument("--format", dest="fmt", choices=("y4m", "npy"), default="y4m")
     tb.add_argument("--matrix", dest="out_matrix", choices=("601", "709"), default=None, help="YUV matrix of the Y4M tubes (default: the video's, else 601)")
     tb.add_argument("--range", dest="out_range", choices=("limited", "full"), default=None, help="sample range of the Y4M tubes")
-    tb.add_argument("--index", default=None, help="write `file picture T track X0 Y0 L` per picture")
+    tb.add_argument("--align", action="store_true", help="roll-aligned tubes: the windows are turned so that the eye line of the landmarks, "
+                    "smoothed like the centre, is horizontal (needs the landmarks file)")
+    tb.add_argument("--index", default=None, help="write `file picture T track X0 Y0 L` per picture (with --align: `... track CX CY BX BY K`)")
     return ap
 
 
@@ -1210,7 +1216,8 @@ def main(argv=None):
             res = tube(v, a.tracking, a.rest[0] if len(a.rest) == 2 else None, a.rest[-1], size=a.size, region=a.region, scale=a.scale,
                        smooth=a.smooth, label=a.label, only=a.only, segments=a.segments, min_length=a.min_length, t_from=a.t_from,
                        t_until=a.t_until, fmt=a.fmt, matrix=a.out_matrix or a.matrix or getattr(v, "matrix", "601"),
-                       full_range=(rng == "full") if rng is not None else bool(getattr(v, "full_range", False)), index=a.index, fps=a.fps, ctx=ctx)
+                       full_range=(rng == "full") if rng is not None else bool(getattr(v, "full_range", False)), index=a.index, fps=a.fps, ctx=ctx,
+                       align=a.align)
         except (KeyError, ValueError) as e:
             ap.error(str(e.args[0]) if e.args else str(e))
     elif a.verb == "extract":

@@ -786,18 +786,26 @@ class Context(object):
         """the windows (X0, Y0, L), in sixteenths of a pixel, of resident frames as size x size pictures (pvf_frame_crops): uint8
         [n, size, size, 3] for layout "rgb", [n, picture bytes] (Y, U, V tight) for "yuv420".  With out_ptr, a device address that holds
         as much, the pictures stay in HBM and nothing is returned."""
+        return self._frame_pictures("frame_crops", self._l.pvf_frame_crops, 3, frames, windows, size, layout, matrix, full_range, out_ptr)
+
+    def frame_warps(self, frames, windows, size, layout="rgb", matrix="601", full_range=False, out_ptr=None):
+        """the oriented windows (CX, CY, BX, BY, K) of resident frames (TUBE.md "Oriented window", pvf_frame_warps) as size x size
+        pictures: what frame_crops returns, through windows that need not be axis-aligned"""
+        return self._frame_pictures("frame_warps", self._l.pvf_frame_warps, 5, frames, windows, size, layout, matrix, full_range, out_ptr)
+
+    def _frame_pictures(self, name, call, per_window, frames, windows, size, layout, matrix, full_range, out_ptr):
         if str(layout) not in ("rgb", "yuv420"):
             raise ValueError("layout must be 'rgb' or 'yuv420', not %r" % (layout,))
-        windows = np.ascontiguousarray(windows, np.int32).reshape(-1, 3)
+        windows = np.ascontiguousarray(windows, np.int32).reshape(-1, per_window)
         n, size = len(windows), int(size)
         if len(frames) != n:
-            raise ValueError("frame_crops: one frame per window")
+            raise ValueError("%s: one frame per window" % name)
         flags = _yuv_flags(matrix, full_range) | (4 if layout == "yuv420" else 0)      # PVF_CROP_YUV420
         shape = (n, size, size, 3) if layout == "rgb" else (n, size * size + 2 * ((size + 1) // 2) ** 2)
         out = None if out_ptr is not None else np.empty(shape if size > 0 else (n, 0), np.uint8)
         with self._staging():
-            check(self._l.pvf_frame_crops(self._h, ptr(self._handles(frames)), ptr(windows), n, size, flags,
-                                          C.c_void_p(int(out_ptr)) if out_ptr is not None else ptr(out), 1 if out_ptr is not None else 0))
+            check(call(self._h, ptr(self._handles(frames)), ptr(windows), n, size, flags,
+                       C.c_void_p(int(out_ptr)) if out_ptr is not None else ptr(out), 1 if out_ptr is not None else 0))
         return out
 
     @staticmethod

@@ -12,6 +12,7 @@ MIN_SIZE, MAX_SIZE = 1, 1024             # PVF_CROP_MIN_SIZE, PVF_CROP_MAX_SIZE
 MIN_SIDE, MAX_SIDE = 16, 1 << 18         # PVF_CROP_MIN_SIDE, PVF_CROP_MAX_SIDE
 MAX_COORD = 1 << 30                      # PVF_CROP_MAX_COORD
 MAX_CROPS = 65536                        # PVF_CROP_MAX_CROPS
+MAX_K, MAX_STEP = 16, 1 << 20            # PVF_WARP_MAX_K, PVF_WARP_MAX_STEP
 SCALE = {"face": 1.6, "mouth": 0.5}
 MAX_OPEN = 64                            # tube files open at a time (FilePool)
 
@@ -56,6 +57,43 @@ def quantise(cx, cy, side):
     return min(max(X0, -MAX_COORD), MAX_COORD), min(max(Y0, -MAX_COORD), MAX_COORD), L
 
 
+def eye_direction(pts):
+    """the unit vector from the mean of points 36 .. 41 to the mean of points 42 .. 47 (integer sums, each divided by 6.0): the row
+    direction of an aligned window.  (1.0, 0.0) for coincident eyes or a face without points."""
+    if pts is None:
+        return 1.0, 0.0
+    p = np.asarray(pts).reshape(68, 2)
+    e0x, e0y = sum(int(v) for v in p[36:42, 0]) / 6.0, sum(int(v) for v in p[36:42, 1]) / 6.0
+    e1x, e1y = sum(int(v) for v in p[42:48, 0]) / 6.0, sum(int(v) for v in p[42:48, 1]) / 6.0
+    return unit(e1x - e0x, e1y - e0y)
+
+
+def unit(dx, dy):
+    """(dx, dy) / hypot(dx, dy); (1.0, 0.0) for a vector of length 0"""
+    length = math.hypot(dx, dy)
+    return (dx / length, dy / length) if length > 0.0 else (1.0, 0.0)
+
+
+def quantise_oriented(cx, cy, side, c, s, S):
+    """centre, side and unit row direction -> (CX, CY, BX, BY, K) for pictures of side S (TUBE.md "Oriented window"):
+    CX = floor(16 cx + 0.5); A = (side / S) 65536 (c, s); K the smallest of 1 .. MAX_K with (65536 K)^2 >= AX^2 + AY^2 on the components
+    rounded half up to integers (MAX_K if none); B = floor(A / K + 0.5), clipped to +-MAX_STEP"""
+    CX = min(max(int(math.floor(16.0 * float(cx) + 0.5)), -MAX_COORD), MAX_COORD)
+    CY = min(max(int(math.floor(16.0 * float(cy) + 0.5)), -MAX_COORD), MAX_COORD)
+    lim = float(MAX_K * MAX_STEP * 2)                            # (a step beyond it is clipped to the cap whatever K is)
+    ax = min(max(float(side) / float(S) * 65536.0 * float(c), -lim), lim)
+    ay = min(max(float(side) / float(S) * 65536.0 * float(s), -lim), lim)
+    AX, AY = int(math.floor(ax + 0.5)), int(math.floor(ay + 0.5))
+    K = MAX_K
+    for k in range(1, MAX_K):
+        if (65536 * k) ** 2 >= AX * AX + AY * AY:
+            K = k
+            break
+    BX = min(max(int(math.floor(ax / K + 0.5)), -MAX_STEP), MAX_STEP)
+    BY = min(max(int(math.floor(ay / K + 0.5)), -MAX_STEP), MAX_STEP)
+    return CX, CY, BX, BY, K
+
+
 def read_segments(path):
     """`track start end ...` lines, what `talk --segments` writes -> [(track, start, end)] in file order"""
     out = []
@@ -71,10 +109,10 @@ def read_segments(path):
 
 
 def plan(faces, region="face", scale=None, smooth_window=0.5, labels=None, only=None, segments=None, min_length=0.0, t_from=0.0, t_until=None,
-         ext="npy"):
+         ext="npy", align=False, size=None):
     """faces: [(T, track, frame index, box, points or None)] in any order -> [(file name, track, [(face index, T, (X0, Y0, L))])] by
-    track, then span.  A track's windows are smoothed over all its rows, whatever is selected afterwards: --from / --until, a span
-    (ms(start) <= ms(T) <= ms(end)) and --min-length (ms(last T) - ms(first T) >= ms(min_length)) only choose among them."""
+    track, then span; with align, for pictures of side `size`, the windows are (CX, CY, BX, BY, K) along the smoothed eye line.
+    A track's windows are smoothed over all its rows, whatever is selected afterwards: --from / --until, a span (ms(start) <= ms(T) <= ms(end)) and --min-length (ms(last T) - ms(first T) >= ms(min_length)) only choose among them."""
     if region not in SCALE:
         raise ValueError("tube: the region is face or mouth")
     scale = SCALE[region] if scale is None else float(scale)
@@ -93,7 +131,15 @@ def plan(faces, region="face", scale=None, smooth_window=0.5, labels=None, only=
             raw = [mouth_region(faces[i][3], faces[i][4], scale) for i in idx]
         times = [faces[i][0] for i in idx]
         sm = [smooth(times, [r[k] for r in raw], smooth_window) for k in range(3)]
-        rows = [(i, faces[i][0], quantise(sm[0][k], sm[1][k], sm[2][k])) for k, i in enumerate(idx)]
+        if align:
+            # the direction is smoothed as a vector, component by component, and made a unit vector again: a track that passes +-180
+            # degrees stays there; with --smooth 0 it is the raw direction
+            dirs = [eye_direction(faces[i][4]) for i in idx]
+            if ms(smooth_window) > 0:
+                dirs = [unit(x, y) for x, y in zip(smooth(times, [d[0] for d in dirs], smooth_window), smooth(times, [d[1] for d in dirs], smooth_window))]
+            rows = [(i, faces[i][0], quantise_oriented(sm[0][k], sm[1][k], sm[2][k], dirs[k][0], dirs[k][1], size)) for k, i in enumerate(idx)]
+        else:
+            rows = [(i, faces[i][0], quantise(sm[0][k], sm[1][k], sm[2][k])) for k, i in enumerate(idx)]
         rows = [r for r in rows if r[1] >= t_from and (t_until is None or r[1] < t_until)]
         if segments is None:
             parts = [("track_%05d.%s" % (track, ext), rows)]
@@ -107,7 +153,8 @@ def plan(faces, region="face", scale=None, smooth_window=0.5, labels=None, only=
 
 
 def index_line(fname, k, T, track, window):
-    return "%s %d %.3f %d %d %d %d\n" % ((fname, k, T, track) + tuple(int(v) for v in window))
+    """`file picture T track X0 Y0 L`, or with an oriented window `file picture T track CX CY BX BY K`"""
+    return "%s %d %.3f %d" % (fname, k, T, track) + "".join(" %d" % int(v) for v in window) + "\n"
 
 
 class FilePool(object):

@@ -6,7 +6,11 @@ HBM peak the kernel time makes of them.  Two yardsticks from code older than the
 family of pvf_face_chips for as many faces on the same frames, (b) the device-to-host copy of the call's own output alone.
 Writes one JSON object to --out (default profiles/tube_n4096.json) and prints it.
 
-    python tools/bench_tube.py [--crops 4096] [--frames 64] [--repeats 5]
+--align: the aligned leg on the same windows, made oriented windows (tube.quantise_oriented) with rolls spread
+over +-30 degrees and once more at 0 degrees: pvf_frame_warps' kernel beside pvf_frame_crops' on the same windows, the copy of the same
+pictures to the host and the chip step of as many faces, all in this run.  Writes profiles/tube_align_n4096.json.
+
+    python tools/bench_tube.py [--crops 4096] [--frames 64] [--repeats 5] [--align]
     rocprofv3 --kernel-trace --stats -d <dir> -- python tools/bench_tube.py --kernel-only 10
 
 --kernel-only N: nothing but N frame_crops calls into device memory (S = 224, RGB), for a kernel trace of its own."""
@@ -30,8 +34,11 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=3, help="calls per timed window")
     ap.add_argument("--kernel-only", type=int, default=0, metavar="N")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tube_n4096.json"))
+    ap.add_argument("--align", action="store_true", help="the aligned leg: warp_k beside crop_k, the copy and the chip step")
+    ap.add_argument("--out", default=None, help="default: profiles/tube_n4096.json, with --align profiles/tube_align_n4096.json")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "tube_align_n4096.json" if a.align else "tube_n4096.json")
     import numpy as np
     import torch
     torch.cuda.set_device(0)
@@ -83,7 +90,45 @@ def main():
     chips()
     chip_ms = sorted(family(chips, "chip") for _ in range(a.repeats))
     configs = {}
-    for S in (224, 96):
+    if a.align:
+        import math
+        from pyannote_video_amd import tube
+        rolls = rng.uniform(-30.0, 30.0, n)
+
+        def oriented(S, degrees):
+            return np.array([tube.quantise_oriented((x + L / 2.0) / 16.0, (y + L / 2.0) / 16.0, L / 16.0, math.cos(math.radians(d)),
+                                                    math.sin(math.radians(d)), S) for (x, y, L), d in zip(win.tolist(), degrees)], np.int32)
+        for S in (224, 96):
+            for layout in ("rgb", "yuv420"):
+                out_bytes = n * (S * S * 3 if layout == "rgb" else S * S + 2 * ((S + 1) // 2) ** 2)
+                dbuf = torch.empty(out_bytes, dtype=torch.uint8, device="cuda")
+                legs = {"rolls_within_30_degrees": oriented(S, rolls), "roll_0": oriented(S, np.zeros(n))}
+                calls = dict((k, (lambda w: (lambda: ctx.frame_warps(handles, w, S, layout, out_ptr=dbuf.data_ptr())))(w)) for k, w in legs.items())
+                calls["crop_k_same_windows"] = lambda: ctx.frame_crops(handles, win, S, layout, out_ptr=dbuf.data_ptr())
+                host = lambda: ctx.frame_warps(handles, legs["rolls_within_30_degrees"], S, layout)
+                for c in list(calls.values()) + [host]:
+                    c()                                             # warm-up
+                kern = dict((k, sorted(family(c, "tube") for _ in range(a.repeats))) for k, c in calls.items())
+                ms_host = [round(window(host), 4) for _ in range(a.repeats)]
+
+                def copy():
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    dbuf.cpu()
+                    return (time.perf_counter() - t0) * 1e3
+                copy()
+                copy_ms = sorted(round(copy(), 4) for _ in range(a.repeats))
+                k = med(kern["rolls_within_30_degrees"])
+                configs["S%d_%s" % (S, layout)] = {
+                    "picture_bytes_out": out_bytes, "window_bytes_in": window_bytes,
+                    "sub_samples_per_axis": dict((str(int(v)), int((legs["rolls_within_30_degrees"][:, 4] == v).sum()))
+                                                 for v in np.unique(legs["rolls_within_30_degrees"][:, 4])),
+                    "kernel_ms_per_call_to_device": kern, "ms_per_call_host_clock_to_host": ms_host,
+                    "copy_of_the_output_to_host_ms": copy_ms,
+                    "warp_over_crop": round(k / med(kern["crop_k_same_windows"]), 4), "warp_over_copy": round(k / med(copy_ms), 4),
+                    "warp_over_chip": round(k / med(chip_ms), 4), "warp_below_copy": bool(k < med(copy_ms)),
+                }
+    for S in (() if a.align else (224, 96)):
         for layout in ("rgb", "yuv420"):
             out_bytes = n * (S * S * 3 if layout == "rgb" else S * S + 2 * ((S + 1) // 2) ** 2)
             dbuf = torch.empty(out_bytes, dtype=torch.uint8, device="cuda")
@@ -115,7 +160,7 @@ def main():
                 "kernel_below_copy": bool(k < med(copy_ms)), "kernel_not_slower_than_chip": bool(k <= med(chip_ms)),
             }
     line = {
-        "bench": "tube: %d crops of 1080p frames, %d per frame, L / 16 in 150 .. 500" % (n, PER_FRAME), "crops": n, "frames": a.frames,
+        "bench": ("tube --align: %d oriented windows" if a.align else "tube: %d crops") % n + " of 1080p frames, %d per frame, L / 16 in 150 .. 500" % PER_FRAME, "crops": n, "frames": a.frames,
         "repeats": a.repeats, "calls_per_window": a.rounds, "hbm_peak_bytes_per_second": HBM_PEAK,
         "chip_family_ms_for_as_many_faces": chip_ms, "configurations": configs,
     }
