@@ -74,11 +74,20 @@ __device__ __forceinline__ void bfly(double2& a, double2& b, double wr, double w
 // element x_br[k] never moves from position brev6(k), hence the OUTPUT IS LEFT IN BIT-REVERSED POSITIONS along both axes:
 //   X[kr][kc]  is found at  s[brev6(kr) * LP + brev6(kc)]            (use FFT_AT below).
 #define FFT_AT(s, r, c) (s)[brev6(r) * LP + brev6(c)]
-template <int NT = 256>     // threads of the block: 256 (two line tasks per thread and phase) or 512 (one)
-__device__ __forceinline__ void fft2d_lds(double2* s, const double* __restrict__ tw, bool inverse)
+// `before_last` runs once, ahead of the barrier in front of the last phase: the place from which a caller's global loads (the values
+// it will combine with the spectrum) have that barrier and a whole phase of butterflies to arrive behind.
+struct FftNoHook { __device__ __forceinline__ void operator()() const {} };
+template <int NT = 256, class Hook = FftNoHook>     // NT threads of the block: 256 (two line tasks per thread and phase) or 512 (one)
+__device__ __forceinline__ void fft2d_lds(double2* s, const double* __restrict__ twg, bool inverse, Hook before_last = Hook())
 {
     const int tid = threadIdx.x;
     const double sg = inverse ? 1.0 : -1.0;      // wi = +sin (inverse) / -sin (forward)
+    // Every twiddle of a wave's task is the same for its 64 lanes: phase 1 uses tw[0], tw[32], tw[16 j], phase 2 indexes with b, the
+    // wave's number.  So the table is read through the scalar cache (constant address space: no kernel stores to it) and the factors
+    // reach the butterflies' products as scalar operands -- up to 14 doubles that held 28 vector registers per phase when they came
+    // out of LDS, and spilled 19 in the fused kernels at their 128-register budget.
+    const __attribute__((address_space(4))) double* tw = (const __attribute__((address_space(4))) double*)twg;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
 #pragma unroll
     for (int pass = 0; pass < 2; ++pass) {
         // ---- phase 1: task (line, q): positions brev6(8q + i) = 8 * brev3(i) + brev3(q)
@@ -109,11 +118,12 @@ __device__ __forceinline__ void fft2d_lds(double2* s, const double* __restrict__
                 s[pass == 0 ? line * LP + pos : pos * LP + line] = e[i];
             }
         }
+        if (pass == 1) before_last();
         __syncthreads();
         // ---- phase 2: task (line, b): x[8a + b] lives at brev6(8a + b) = 8 * brev3(b) + brev3(a)
 #pragma unroll
         for (int u = 0; u < 512 / NT; ++u) {
-            const int tt = tid + NT * u, line = tt & 63, b = tt >> 6;     // a wave = the 64 lines of one b (see the bank note above)
+            const int tt = tid + NT * u, line = tt & 63, b = wv + (NT >> 6) * u;     // a wave = the 64 lines of one b (see the bank note above)
             const int rb = (int)(__brev((unsigned)b) >> 29);
             double2 f[8];
 #pragma unroll
@@ -378,11 +388,17 @@ __global__ void __launch_bounds__(256) peak_k(const TrkJob* __restrict__ jobs, c
 // fp64 latencies of the butterfly chains (a 256-thread form needed > 256 registers and ran one wave per SIMD).
 #define FUSED_NT 512
 #define FUSED_PT (FS * FS / FUSED_NT)
+#define FUSED_EARLY 2                   // update_fused_k: filter values of a plane asked for ahead of the transform's last phase (see there)
 // A thread owns the spectrum points at the LDS positions ph = tid + 512 k, k = 0..7: row (tid >> 6) + 8 k, column tid & 63 (consecutive
 // lanes = neighbouring elements, no bank conflict).  Position (pr, pc) holds X[brev6(pr)][brev6(pc)]; with w = tid >> 6 that is
 // logical row 8 brev3(w) + brev3(k), column brev6(tid & 63): the 8 points of a thread are q0 + 64 brev3(k) -- constant offsets from
 // one address, and a wave's 64 points of one k are one 1 KB row of A (permuted).
 struct FusedOwn { int lds0; int q0; };
+// the filters lie in global memory: global_*, not flat_*, instructions (16-byte accesses through a plain vector type)
+typedef double dvec2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(1))) dvec2 gdouble2;
+__device__ __forceinline__ double2 fused_ldg(const gdouble2* p) { const dvec2 t = *p; return make_double2(t.x, t.y); }
+__device__ __forceinline__ void fused_stg(gdouble2* p, double re, double im) { dvec2 t; t.x = re; t.y = im; *p = t; }
 __device__ __forceinline__ FusedOwn fused_own()
 {
     const int tid = threadIdx.x, w = tid >> 6;
@@ -392,26 +408,36 @@ __device__ __forceinline__ FusedOwn fused_own()
 #define FUSED_LDS(k) (8 * LP * (k))                                                        // k-th owned LDS position, from lds0
 #define FUSED_Q(k) (FS * ((((k) & 1) << 2) | ((k) & 2) | (((k) >> 2) & 1)))                // k-th owned logical index, from q0
 
-// plane i of the tracker's features -> mask * value -> s.  All eight loads of a thread are issued before the first is used
-// (the plane test is block-uniform: no branch inside the element loop).
-__device__ __forceinline__ void fused_load_plane(double2* s, const uint8_t* __restrict__ chip, const uint8_t* __restrict__ rec, int i,
-                                                 const double* __restrict__ mask64)
+// plane i of the tracker's features -> mask * value -> s, in two steps so that the record's bytes of plane i + 1 can be asked for
+// while plane i is still being transformed (fused_fetch_plane from the transform's hook, fused_store_plane after the plane's last
+// barrier).  All loads of a thread are issued before the first is used (the plane tests are block-uniform: no branch inside the
+// element loops).  The grey plane (31) reads 24 single bytes of the chip; it is fetched where it is stored.
+struct FusedRaw { float4 lo, hi; uint2 ab; };
+__device__ __forceinline__ void fused_fetch_plane(FusedRaw& r, const uint8_t* __restrict__ rec, int i)
 {
     const int tid = threadIdx.x;
-    float v[FUSED_PT];
-    double m[FUSED_PT];
     static_assert(FUSED_NT == 512 && FUSED_PT == 8, "the record's slot order is made for 512 threads x 8 pixels");
     if (i < 31) {
         // the thread's eight pixels tid + 512 k: 32 consecutive bytes of a float array, 8 of the bins (TRKF_SLOT)
         const float4* pl = reinterpret_cast<const float4*>(reinterpret_cast<const float*>(rec) + (i < 27 ? 0 : (size_t)(i - 26) * TRKF_PLANE) + tid * 8);
-        const float4 lo = pl[0], hi = pl[1];
-        v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w; v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
+        r.lo = pl[0]; r.hi = pl[1];
+        if (i < 27) r.ab = *reinterpret_cast<const uint2*>(rec + TRKF_A + tid * 8);
+    }
+}
+
+__device__ __forceinline__ void fused_store_plane(double2* s, const uint8_t* __restrict__ chip, const FusedRaw& r, int i,
+                                                  const double* __restrict__ mask64)
+{
+    const int tid = threadIdx.x;
+    float v[FUSED_PT];
+    double m[FUSED_PT];
+    if (i < 31) {
+        v[0] = r.lo.x; v[1] = r.lo.y; v[2] = r.lo.z; v[3] = r.lo.w; v[4] = r.hi.x; v[5] = r.hi.y; v[6] = r.hi.z; v[7] = r.hi.w;
         if (i < 27) {
-            const uint2 ab = *reinterpret_cast<const uint2*>(rec + TRKF_A + tid * 8);
             const int want = i < 18 ? i : i - 18;
 #pragma unroll
             for (int k = 0; k < FUSED_PT; ++k) {
-                const int a = (int)(((k < 4 ? ab.x : ab.y) >> (8 * (k & 3))) & 0xffu);
+                const int a = (int)(((k < 4 ? r.ab.x : r.ab.y) >> (8 * (k & 3))) & 0xffu);
                 const int key = i < 18 ? a : (a >= 9 ? a - 9 : a);
                 v[k] = key == want ? v[k] : 0.0f;
             }
@@ -433,12 +459,8 @@ __global__ void __launch_bounds__(FUSED_NT) __attribute__((amdgpu_waves_per_eu(4
                                                           const double* __restrict__ mask64, const double* __restrict__ tw64)
 {
     extern __shared__ __attribute__((aligned(16))) double2 s[];
-    __shared__ double tw_lds[2 * FS];           // twiddles next to the data: re-read after every barrier instead of pinned in registers
-    const int b = blockIdx.x, tid = threadIdx.x;
+    const int b = blockIdx.x;
     const TrkJob j = jobs[b];
-    if (tid < 2 * FS) tw_lds[tid] = tw64[tid];
-    __syncthreads();
-    tw64 = tw_lds;
     make_target_lds<FUSED_NT>(s, j.cx, j.cy, tw64);
     const FusedOwn own = fused_own();
     double2 g[FUSED_PT];
@@ -448,20 +470,22 @@ __global__ void __launch_bounds__(FUSED_NT) __attribute__((amdgpu_waves_per_eu(4
     double bsum[FUSED_PT];
 #pragma unroll
     for (int k = 0; k < FUSED_PT; ++k) bsum[k] = 0;
-    double2* A = reinterpret_cast<double2*>(j.state + TRK_A) + own.q0;
+    gdouble2* A = (gdouble2*)reinterpret_cast<double2*>(j.state + TRK_A) + own.q0;
     const uint8_t* chip = chips + (size_t)b * FS * FS * 3;
     const uint8_t* fb = feat + (size_t)b * TRKF_BYTES;
+    FusedRaw raw;
+    fused_fetch_plane(raw, fb, 0);
     for (int i = 0; i < NPL; ++i) {
         const double* mk = mask64;
         asm volatile("" : "+s"(mk));               // the window is re-read per plane (L1/L2 hits), not kept in 16 registers across the loop
-        fused_load_plane(s, chip, fb, i, mk);
+        fused_store_plane(s, chip, raw, i, mk);
         __syncthreads();
-        fft2d_lds<FUSED_NT>(s, tw64, false);
-        double2* Ai = A + (size_t)i * FS * FS;
+        fft2d_lds<FUSED_NT>(s, tw64, false, [&]() { if (i + 1 < NPL) fused_fetch_plane(raw, fb, i + 1); });
+        gdouble2* Ai = A + (size_t)i * FS * FS;
 #pragma unroll
         for (int k = 0; k < FUSED_PT; ++k) {
             const double2 f = s[own.lds0 + FUSED_LDS(k)];
-            Ai[FUSED_Q(k)] = make_double2(g[k].x * f.x - g[k].y * f.y, g[k].x * f.y + g[k].y * f.x);
+            fused_stg(Ai + FUSED_Q(k), g[k].x * f.x - g[k].y * f.y, g[k].x * f.y + g[k].y * f.x);
             bsum[k] = bsum[k] + (f.x * f.x + f.y * f.y);
         }
         __syncthreads();
@@ -477,29 +501,34 @@ __global__ void __launch_bounds__(FUSED_NT) __attribute__((amdgpu_waves_per_eu(4
                                                            const double* __restrict__ mask64, const double* __restrict__ tw64, double* __restrict__ results)
 {
     extern __shared__ __attribute__((aligned(16))) double2 s[];
-    __shared__ double tw_lds[2 * FS];
-    const int b = blockIdx.x, tid = threadIdx.x;
+    const int b = blockIdx.x;
     const TrkJob j = jobs[b];
-    if (tid < 2 * FS) tw_lds[tid] = tw64[tid];
-    __syncthreads();
-    tw64 = tw_lds;
     const FusedOwn own = fused_own();
-    const double2* A = reinterpret_cast<const double2*>(j.state + TRK_A) + own.q0;
+    const gdouble2* A = (const gdouble2*)reinterpret_cast<const double2*>(j.state + TRK_A) + own.q0;
     const uint8_t* chip = chips + (size_t)b * FS * FS * 3;
     const uint8_t* fb = feat + (size_t)b * TRKF_BYTES;
     double gr[FUSED_PT], gi[FUSED_PT];
 #pragma unroll
     for (int k = 0; k < FUSED_PT; ++k) { gr[k] = 0; gi[k] = 0; }
+    FusedRaw raw;
+    fused_fetch_plane(raw, fb, 0);
     for (int i = 0; i < NPL; ++i) {
         const double* mk = mask64;
         asm volatile("" : "+s"(mk));
-        fused_load_plane(s, chip, fb, i, mk);
+        fused_store_plane(s, chip, raw, i, mk);
         __syncthreads();
-        fft2d_lds<FUSED_NT>(s, tw64, false);
-        const double2* Ai = A + (size_t)i * FS * FS;
+        const gdouble2* Ai = A + (size_t)i * FS * FS;
         double2 a[FUSED_PT];
+        // Ahead of the transform's last phase: the next plane's record (L2) and the first FUSED_EARLY of this plane's eight filter
+        // values (HBM).  More of them do not fit beside the phase's butterflies in 128 registers: four spill 8 registers, all eight 26,
+        // and both measured slower than two (profiles/tracker_registers.txt).  The rest follow the transform, as before.
+        fft2d_lds<FUSED_NT>(s, tw64, false, [&]() {
 #pragma unroll
-        for (int k = 0; k < FUSED_PT; ++k) a[k] = Ai[FUSED_Q(k)];         // all eight in flight together
+            for (int k = 0; k < FUSED_EARLY; ++k) a[k] = fused_ldg(Ai + FUSED_Q(k));
+            if (i + 1 < NPL) fused_fetch_plane(raw, fb, i + 1);
+        });
+#pragma unroll
+        for (int k = FUSED_EARLY; k < FUSED_PT; ++k) a[k] = fused_ldg(Ai + FUSED_Q(k));       // in flight together
 #pragma unroll
         for (int k = 0; k < FUSED_PT; ++k) {
             const double2 f = s[own.lds0 + FUSED_LDS(k)];
