@@ -261,9 +261,16 @@ int32_t pvf_associate(const double* trackers, int32_t n_trackers, const double* 
 int32_t pvf_munkres(const double* cost, int32_t n, int32_t* row_to_col);
 
 /* ---- S4 landmarks + embedding ---------------------------------------------------------------------- */
-/* ref: face.py:69-70  self.shape_predictor_(rgb, face) -> 68 integer points; face i lives on frames[i] */
+/* ref: face.py:69-70  self.shape_predictor_(rgb, face) -> 68 integer points; face i lives on frames[i].
+ * Any int32 box is accepted: zero-area (68 identical points), inverted, off the frame (off-frame pixels read as 0).  The final points
+ * SATURATE to the int32 range: floor(x + 0.5) is clamped to [-2^31, 2^31 - 1] as a double, then converted (dlib's behaviour for such
+ * boxes is not known: oracle/EXT_REGISTER.md E25).  n = 0 does nothing; refused: n < 0, null pointers with n > 0. */
 int32_t pvf_landmarks(pvf_handle ctx, const pvf_handle* frames, const pvf_rect_i32* boxes, int32_t n,
                       int32_t* pts /* n*68*2 */);
+/* pvf_landmarks, also returning the float32 shape the last cascade left, in normalised box coordinates (x = left + u * (right - left)):
+ * what the integer points are rounded from.  For tests of the order of the kernel's sums. */
+int32_t pvf_debug_landmarks_shape(pvf_handle ctx, const pvf_handle* frames, const pvf_rect_i32* boxes, int32_t n,
+                                  int32_t* pts /* n*68*2 */, float* shape /* n*68*2 */);
 /* ref: face.py:73-76  face_recognition_.compute_face_descriptor(rgb, landmarks) -> 128 floats */
 int32_t pvf_embed(pvf_handle ctx, const pvf_handle* frames, const int32_t* pts /* n*68*2 */, int32_t n,
                   float* out /* n*128 */);

@@ -184,6 +184,15 @@ class ShapePredictor(object):
         lib().pvo_landmarks(_p(rgb), rgb.shape[0], rgb.shape[1], _p(r), C.byref(self.s), _p(pts))
         return pts
 
+    def shape_f32(self, rgb, rect):
+        """(points, shape): the integer points of __call__ and the float32 [n_parts, 2] shape after the last cascade they are rounded from"""
+        rgb = _u8(rgb)
+        r = np.asarray(rect, np.int32)
+        pts = np.zeros((self.n_parts, 2), np.int32)
+        shape = np.zeros((self.n_parts, 2), np.float32)
+        lib().pvo_landmarks_f32(_p(rgb), rgb.shape[0], rgb.shape[1], _p(r), C.byref(self.s), _p(pts), _p(shape))
+        return pts, shape
+
 
 class _Embed(C.Structure):
     _fields_ = [("mean_shape_xy", C.c_void_p), ("chip_size", C.c_int), ("chip_padding", C.c_double),

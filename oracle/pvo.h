@@ -107,6 +107,10 @@ typedef struct {
 } pvo_shape_model;
 void pvo_landmarks(const uint8_t* rgb, int h, int w, const int32_t rect[4], const pvo_shape_model* m,
                    int32_t* pts /* [n_parts][2] */);
+/* the same, also writing the float32 shape after the last cascade (normalised box coordinates) unless shape is NULL; the final points
+ * saturate to the int32 range (EXT_REGISTER.md E25) */
+void pvo_landmarks_f32(const uint8_t* rgb, int h, int w, const int32_t rect[4], const pvo_shape_model* m,
+                       int32_t* pts /* [n_parts][2] */, float* shape /* [n_parts][2] or NULL */);
 
 /* ---------------------------------------------------------------- face chip + ResNet (pvo_resnet.c) */
 typedef struct {

@@ -31,7 +31,15 @@ static void similarity_linear(const float* from, const float* to, int n, float M
     M[2] = (float)cb; M[3] = (float)ca;
 }
 
-void pvo_landmarks(const uint8_t* rgb, int h, int w, const int32_t rect[4], const pvo_shape_model* m, int32_t* pts)
+/* The final points SATURATE to the int32 range: the double is clamped, then converted, so boxes at the int32 extremes give the same
+ * integers on every platform (an out-of-range double -> int32 conversion is undefined in C: x86 gives INT32_MIN, the GPU saturates).
+ * fmax / fmin drop a NaN operand, so a NaN coordinate (an infinite shape on a zero-area box) gives INT32_MIN.  [EXT] dlib's own
+ * behaviour there is not known (EXT_REGISTER.md E25). */
+static int32_t sat_i32(double v) { return (int32_t)fmin(fmax(v, -2147483648.0), 2147483647.0); }
+
+/* pvo_landmarks, also writing the 2 * n_parts float32 values of the shape after the last cascade (normalised box coordinates: what the
+ * integer points are rounded from) when shape is not NULL */
+void pvo_landmarks_f32(const uint8_t* rgb, int h, int w, const int32_t rect[4], const pvo_shape_model* m, int32_t* pts, float* shape)
 {
     const int P = m->n_parts, NP = m->n_pix, T = m->n_trees;
     const int n_split = (1 << m->depth) - 1, n_leaf = 1 << m->depth;
@@ -70,8 +78,14 @@ void pvo_landmarks(const uint8_t* rgb, int h, int w, const int32_t rect[4], cons
     }
     for (int i = 0; i < P; ++i) {
         const double X = (double)cur[2 * i] * sx + ox, Y = (double)cur[2 * i + 1] * sy + oy;
-        pts[2 * i] = (int32_t)floor(X + 0.5);
-        pts[2 * i + 1] = (int32_t)floor(Y + 0.5);
+        pts[2 * i] = sat_i32(floor(X + 0.5));
+        pts[2 * i + 1] = sat_i32(floor(Y + 0.5));
     }
+    if (shape) memcpy(shape, cur, sizeof(float) * 2 * P);
     free(cur); free(pix);
+}
+
+void pvo_landmarks(const uint8_t* rgb, int h, int w, const int32_t rect[4], const pvo_shape_model* m, int32_t* pts)
+{
+    pvo_landmarks_f32(rgb, h, w, rect, m, pts, NULL);
 }

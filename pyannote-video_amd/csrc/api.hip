@@ -669,10 +669,25 @@ extern "C" int32_t pvf_landmarks(pvf_handle h, const pvf_handle* frames, const p
 {
     API_BEGIN
     ENTER(c, h);
+    PVF_REQUIRE(n >= 0 && ((frames && boxes && pts) || n == 0), "pvf_landmarks: bad arguments");
     if (n == 0) return 0;
     std::vector<Frame> f(n);
     for (int i = 0; i < n; ++i) f[i] = c->frame(frames[i]);
     ert_run(c, f, boxes, n, pts);
+    API_END
+}
+
+// the landmarks and, beside them, the float32 shape the last cascade left (normalised box coordinates, [n][68][2]): what the integer
+// points are rounded from, for tests that compare the order of the kernel's sums with the oracle's bit for bit
+extern "C" int32_t pvf_debug_landmarks_shape(pvf_handle h, const pvf_handle* frames, const pvf_rect_i32* boxes, int32_t n, int32_t* pts, float* shape)
+{
+    API_BEGIN
+    ENTER(c, h);
+    PVF_REQUIRE(n >= 0 && ((frames && boxes && pts && shape) || n == 0), "pvf_debug_landmarks_shape: bad arguments");
+    if (n == 0) return 0;
+    std::vector<Frame> f(n);
+    for (int i = 0; i < n; ++i) f[i] = c->frame(frames[i]);
+    ert_run(c, f, boxes, n, pts, shape);
     API_END
 }
 
@@ -724,6 +739,7 @@ extern "C" int32_t pvf_landmarks_embed(pvf_handle h, const pvf_handle* frames, c
 {
     API_BEGIN
     ENTER(c, h);
+    PVF_REQUIRE(n >= 0, "pvf_landmarks_embed: bad arguments");
     if (n == 0) return 0;
     PVF_REQUIRE(frames && boxes && pts && out, "pvf_landmarks_embed: bad arguments");
     {

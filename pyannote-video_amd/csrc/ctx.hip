@@ -115,11 +115,24 @@ static void load_detector(Ctx* c, const char* path)
     d.loaded = true;
 }
 
+static void free_shape_arrays(ShapeModel& s)
+{
+    void* const arrays[7] = {s.d_initial, s.d_anchor, s.d_deltas, s.d_idx1, s.d_idx2, s.d_thresh, s.d_leaves};
+    for (void* a : arrays)
+        if (a) (void)hipFree(a);
+    s.d_initial = s.d_deltas = s.d_thresh = s.d_leaves = nullptr;
+    s.d_anchor = s.d_idx1 = s.d_idx2 = nullptr;
+}
+
+// Everything is read, checked and uploaded into a model of its own; the context's model is replaced (and its seven device arrays freed)
+// only after that, so a refused file leaves the context exactly as it was: sizes, arrays and `loaded`.
 static void load_shape(Ctx* c, const char* path)
 {
     auto m = pvf_read_model(path, 1);
-    const int32_t* q = need(m, "sp.meta").i32();
-    ShapeModel& s = c->shape;
+    const Tensor& meta = need(m, "sp.meta");
+    PVF_REQUIRE(meta.numel() >= 5, "sp.meta too short");
+    const int32_t* q = meta.i32();
+    ShapeModel s;
     s.n_cascades = q[0]; s.n_trees = q[1]; s.n_parts = q[2]; s.n_pix = q[3]; s.depth = q[4];
     PVF_REQUIRE(s.n_parts == 68, "shape predictor: 68 parts expected");
     PVF_REQUIRE(s.depth >= 1 && s.depth <= 6, "shape predictor: tree depth 1..6");
@@ -142,14 +155,21 @@ static void load_shape(Ctx* c, const char* path)
     }
     auto up_f = [&](const char* k) { const Tensor& t = need(m, k); return upload<float>(t.f32(), t.numel()); };
     auto up_i = [&](const char* k) { const Tensor& t = need(m, k); return upload<int32_t>(t.i32(), t.numel()); };
-    s.d_initial = up_f("sp.initial_shape");
-    s.d_anchor = up_i("sp.anchor_idx");
-    s.d_deltas = up_f("sp.deltas");
-    s.d_idx1 = up_i("sp.split_idx1");
-    s.d_idx2 = up_i("sp.split_idx2");
-    s.d_thresh = up_f("sp.split_thresh");
-    s.d_leaves = up_f("sp.leaves");
+    try {
+        s.d_initial = up_f("sp.initial_shape");
+        s.d_anchor = up_i("sp.anchor_idx");
+        s.d_deltas = up_f("sp.deltas");
+        s.d_idx1 = up_i("sp.split_idx1");
+        s.d_idx2 = up_i("sp.split_idx2");
+        s.d_thresh = up_f("sp.split_thresh");
+        s.d_leaves = up_f("sp.leaves");
+    } catch (...) {
+        free_shape_arrays(s);
+        throw;
+    }
     s.loaded = true;
+    free_shape_arrays(c->shape);       // (hipFree waits for the device: no kernel still reads the old model)
+    c->shape = s;
 }
 
 static const int UNITS[14][3] = {{32, 32, 0}, {32, 32, 0}, {32, 32, 0}, {32, 64, 1}, {64, 64, 0}, {64, 64, 0}, {64, 64, 0},

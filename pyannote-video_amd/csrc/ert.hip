@@ -5,11 +5,15 @@
 
 struct ErtJob { const uint8_t* img; int h, w; int rect[4]; };
 
+// the final points saturate to the int32 range: the double is clamped, then converted (oracle/pvo_ert.c: sat_i32; a NaN gives INT32_MIN)
+__device__ __forceinline__ int32_t sat_i32(double v) { return (int32_t)fmin(fmax(v, -2147483648.0), 2147483647.0); }
+
 __global__ void __launch_bounds__(256) ert_k(const ErtJob* __restrict__ jobs, int n_cascades, int n_trees, int n_parts, int n_pix, int depth,
                                              const float* __restrict__ initial, const int32_t* __restrict__ anchor,
                                              const float* __restrict__ deltas, const int32_t* __restrict__ idx1,
                                              const int32_t* __restrict__ idx2, const float* __restrict__ thresh,
-                                             const float* __restrict__ leaves, int32_t* __restrict__ pts)
+                                             const float* __restrict__ leaves, int32_t* __restrict__ pts,
+                                             float* __restrict__ shape)      // shape: null, or [faces][2 * n_parts], cur after the last cascade
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int P2 = 2 * n_parts;
@@ -88,14 +92,16 @@ __global__ void __launch_bounds__(256) ert_k(const ErtJob* __restrict__ jobs, in
         }
     }
     __syncthreads();
+    if (shape)
+        for (int k = tid; k < P2; k += blockDim.x) shape[(size_t)blockIdx.x * P2 + k] = cur[k];
     for (int i = tid; i < n_parts; i += blockDim.x) {
         const double X = (double)cur[2 * i] * sx + ox, Y = (double)cur[2 * i + 1] * sy + oy;
-        pts[((size_t)blockIdx.x * n_parts + i) * 2] = (int32_t)floor(X + 0.5);
-        pts[((size_t)blockIdx.x * n_parts + i) * 2 + 1] = (int32_t)floor(Y + 0.5);
+        pts[((size_t)blockIdx.x * n_parts + i) * 2] = sat_i32(floor(X + 0.5));
+        pts[((size_t)blockIdx.x * n_parts + i) * 2 + 1] = sat_i32(floor(Y + 0.5));
     }
 }
 
-void ert_run(Ctx* c, const std::vector<Frame>& frames, const pvf_rect_i32* boxes, int n, int32_t* pts)
+void ert_run(Ctx* c, const std::vector<Frame>& frames, const pvf_rect_i32* boxes, int n, int32_t* pts, float* shape)
 {
     const ShapeModel& s = c->shape;
     PVF_REQUIRE(s.loaded, "shape predictor not loaded");
@@ -107,18 +113,21 @@ void ert_run(Ctx* c, const std::vector<Frame>& frames, const pvf_rect_i32* boxes
     }
     ScratchLayout lay;
     const auto sJobs = lay.take<ErtJob>(n, 64); const auto sPts = lay.take<int32_t>((size_t)n * s.n_parts * 2, 64);
+    const auto sShape = lay.take<float>(shape ? (size_t)n * s.n_parts * 2 : 0, 64);
     lay.pad(64);                                              // reason unknown, kept
     c->s_misc.ensure(lay.bytes());
     ErtJob* d_jobs = sJobs.in(c->s_misc); int32_t* d_pts = sPts.in(c->s_misc);
+    float* d_shape = shape ? sShape.in(c->s_misc) : nullptr;
     HIP_CHECK(hipMemcpyAsync(d_jobs, jobs.data(), sJobs.bytes(), hipMemcpyHostToDevice, c->stream));
     const size_t lds = (size_t)(((2 * s.n_parts + 3) & ~3) + ((s.n_pix + 3) & ~3)) * 4 + (size_t)s.n_trees * 4;
     {
         ProfScope ps(c, "ert");
         hipLaunchKernelGGL(ert_k, dim3(n), dim3(256), lds, c->stream, d_jobs, s.n_cascades, s.n_trees,
                            s.n_parts, s.n_pix, s.depth, s.d_initial, s.d_anchor, s.d_deltas, s.d_idx1, s.d_idx2, s.d_thresh, s.d_leaves,
-                           d_pts);
+                           d_pts, d_shape);
     }
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(pts, d_pts, sPts.bytes(), hipMemcpyDeviceToHost, c->stream));
+    if (shape) HIP_CHECK(hipMemcpyAsync(shape, d_shape, sShape.bytes(), hipMemcpyDeviceToHost, c->stream));
     HIP_CHECK(hipStreamSynchronize(c->stream));
 }

@@ -15,6 +15,7 @@
 #include <vector>
 #include "../../include/pvface.h"
 #include "scratch_layout.h"      // PvfError, ScratchLayout
+#include "chip_plan.h"           // ChipJob, ChipDetails, chip_plan_geom
 
 #define PVF_FHOG_STRIDE 32
 
@@ -204,18 +205,6 @@ constexpr size_t TRKF_A = 5 * TRKF_PLANE * sizeof(float);
 constexpr size_t TRKF_BYTES = TRKF_A + TRKF_PLANE;
 #define TRKF_SLOT(q) ((((q) & 511) << 3) | ((q) >> 9))      // where pixel q = 64 y + x sits in each array of the record
 
-// chip extraction plan (host geometry -> device pyramid + bilinear), see chip.hip
-struct ChipJob {
-    // source frame
-    const uint8_t* img; int h, w;
-    // bounding box of the needed sub image (inclusive), and number of pyramid_down<2> levels to build (0 = sample the frame)
-    int bx0, by0, sw, sh, levels;
-    // affine chip -> level image
-    double m[4], b[2];
-    int rows, cols;
-    bool empty;
-};
-struct ChipDetails { double l, t, r, b, cs, sn; int rows, cols; };
 // one job of transform_k (chip.hip): the sub image (x0, y0, sw, sh) of an image of row pitch stride_w, and the affine chip -> sub image
 struct DevXfJob { const uint8_t* src; int stride_w, x0, y0, sw, sh; double m[4], b[2]; };
 
@@ -406,7 +395,7 @@ uint8_t* jitter_scratch(Ctx* c, int faces, int J);
 void jitter_chips_dev(Ctx* c, const uint8_t* d_chips, int n, int J, uint64_t seed, uint8_t* d_out, bool via_transform);
 void jitter_embed_dev(Ctx* c, const uint8_t* d_chips, int n, int J, uint64_t seed, float* out);
 // landmarks (ert.hip)
-void ert_run(Ctx* c, const std::vector<Frame>& frames, const pvf_rect_i32* boxes, int n, int32_t* pts);
+void ert_run(Ctx* c, const std::vector<Frame>& frames, const pvf_rect_i32* boxes, int n, int32_t* pts, float* shape = nullptr);
 // embedding (resnet.hip)
 void face_chip_details(const EmbedModel& m, const int32_t* pts68, ChipDetails* out);
 void dlib_mean_face_shape(float* out /* 51*2 */);      // dlibdat.hip: the shape compiled into dlib, as an embedder file's emb.mean_shape

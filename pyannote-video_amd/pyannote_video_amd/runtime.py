@@ -701,6 +701,19 @@ class Context(object):
             check(self._l.pvf_landmarks(self._h, ptr(self._handles(frames)), ptr(r), n, ptr(pts)))
         return pts
 
+    def landmarks_shape(self, frames, boxes):
+        """(int32 [n, 68, 2], float32 [n, 68, 2]): landmarks() and the float shape of the last cascade, in normalised box coordinates,
+        that they are rounded from (pvf_debug_landmarks_shape)"""
+        n = len(boxes)
+        pts = np.zeros((n, 68, 2), np.int32)
+        shape = np.zeros((n, 68, 2), np.float32)
+        if n == 0:
+            return pts, shape
+        r = _rects(boxes, n)
+        with self._staging():
+            check(self._l.pvf_debug_landmarks_shape(self._h, ptr(self._handles(frames)), ptr(r), n, ptr(pts), ptr(shape)))
+        return pts, shape
+
     def embed(self, frames, pts, num_jitters=0, seed=0):
         """descriptors of the faces; num_jitters > 1: dlib's compute_face_descriptor(img, shape, num_jitters) -- the fp32 mean over
         that many jittered chips per face (JITTER.md), a function of the face, num_jitters and the seed"""
