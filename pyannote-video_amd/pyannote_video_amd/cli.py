@@ -184,97 +184,63 @@ def extract(video, landmark_model, embedding_model, tracking, landmark_output, e
     import queue
     import threading
     from . import pipeline, runtime
+    from .feed import FrameFeed
     jitter = _jitter_kw(num_jitters, jitter_seed)
     ctx = ctx or runtime.default_context()
     ctx.load_shape_predictor(landmark_model)
     ctx.load_embedder(embedding_model)
     frame_width, frame_height = video.frame_size
     rows = formats.read_tracks(tracking)
-    frame_times = [t for t, _ in _times(video)]
-    plan = pipeline.faces_per_frame(rows, frame_times, frame_width, frame_height)
     want = {}
-    for fi, T, g in plan:
+    for fi, T, g in pipeline.faces_per_frame(rows, _frame_times(video, rows), frame_width, frame_height):
         want[fi] = (T, g)
-    last_wanted = max(want) if want else -1
-    q = queue.Queue(maxsize=max(2, int(ahead)))
-    state = {"error": None}
+    state = {"error": None}                  # the writer thread's
+    with FrameFeed(ctx, video, want, ahead=ahead, name="pvface-extract-reader") as feed, \
+            open(landmark_output, 'wb') as flandmark, open(embedding_output, 'wb') as fembedding:
+        pend_f, pend_b, pend_k = [], [], []
+        wq = queue.Queue(maxsize=4)
 
-    def reader():
-        stager = runtime.HostFrameStager(ctx, 16)
-        try:
-            for fi, (t, rgb) in enumerate(video):
-                if fi > last_wanted:
-                    break
-                if fi not in want:
-                    continue
-                rgb, owned = stager.stage(rgb)
-                q.put((fi, rgb, owned))
-            stager.close()
-        except BaseException as e:          # noqa: BLE001 -- re-raised below
-            state["error"] = e
-        finally:
-            q.put(None)
-
-    th = threading.Thread(target=reader, name="pvface-extract-reader")
-    th.start()
-    try:
-        with open(landmark_output, 'wb') as flandmark, open(embedding_output, 'wb') as fembedding:
-            pend_f, pend_b, pend_k, pend_own = [], [], [], []
-            wq = queue.Queue(maxsize=4)
-
-            def writer():
-                # the text of batch i is formatted (in the library, outside the GIL) and written while the GPU computes batch i + 1
-                try:
-                    while True:
-                        item = wq.get()
-                        if item is None:
-                            return
-                        if state["error"] is not None:
-                            continue
-                        T, ident, pts, emb = item
-                        flandmark.write(formats.landmark_rows(T, ident, pts, frame_width, frame_height))
-                        fembedding.write(formats.embedding_rows(T, ident, emb))
-                except BaseException as e:          # noqa: BLE001 -- re-raised below
-                    state["error"] = e
-                    while wq.get() is not None:
-                        pass
-
-            wth = threading.Thread(target=writer, name="pvface-extract-writer")
-            wth.start()
-
-            def flush():
-                if not pend_b:
-                    return
-                pts, emb = ctx.landmarks_embed(pend_f, pend_b, **jitter)
-                wq.put(([k[0] for k in pend_k], [k[1] for k in pend_k], pts, emb))
-                for f in pend_own:
-                    f.release()
-                del pend_f[:], pend_b[:], pend_k[:], pend_own[:]
+        def writer():
+            # the text of batch i is formatted (in the library, outside the GIL) and written while the GPU computes batch i + 1
             try:
-                while state["error"] is None:
-                    item = q.get()
+                while True:
+                    item = wq.get()
                     if item is None:
-                        break
-                    fi, dev, owned = item
-                    T, g = want[fi]
-                    if owned:
-                        pend_own.append(dev)
-                    for ident, box in g:
-                        pend_f.append(dev); pend_b.append(box); pend_k.append((T, ident))
-                    if len(pend_b) >= batch:
-                        flush()
-                if state["error"] is None:
+                        return
+                    if state["error"] is not None:
+                        continue
+                    T, ident, pts, emb = item
+                    flandmark.write(formats.landmark_rows(T, ident, pts, frame_width, frame_height))
+                    fembedding.write(formats.embedding_rows(T, ident, emb))
+            except BaseException as e:          # noqa: BLE001 -- re-raised below
+                state["error"] = e
+                while wq.get() is not None:
+                    pass
+
+        wth = threading.Thread(target=writer, name="pvface-extract-writer")
+        wth.start()
+
+        def flush():
+            if not pend_b:
+                return
+            pts, emb = ctx.landmarks_embed(pend_f, pend_b, **jitter)
+            wq.put(([k[0] for k in pend_k], [k[1] for k in pend_k], pts, emb))
+            feed.release_all(pend_f)
+            del pend_f[:], pend_b[:], pend_k[:]
+        try:
+            for fi, dev in feed:
+                if state["error"] is not None:
+                    break
+                T, g = want[fi]
+                for ident, box in g:
+                    pend_f.append(dev); pend_b.append(box); pend_k.append((T, ident))
+                if len(pend_b) >= batch:
                     flush()
-            finally:
-                wq.put(None)
-                wth.join()
-    finally:
-        while th.is_alive():                 # an error on this side: let the reader run out
-            try:
-                q.get(timeout=0.05)
-            except queue.Empty:
-                pass
-        th.join()
+            if state["error"] is None:
+                flush()
+        finally:
+            wq.put(None)
+            wth.join()
     if state["error"] is not None:
         raise state["error"]
 
@@ -327,9 +293,18 @@ def process(video, shot, landmark_model, embedding_model, tracking_output, landm
     return res
 
 
-def _times(video):
-    n = len(video)
-    return [(i / video.frame_rate, None) for i in range(n)]
+def _load(value, reader):
+    """what a verb was given for one of its input files: a path, read here, or the content as `reader` returns it"""
+    return reader(value) if isinstance(value, str) else value
+
+
+def _frame_times(video, rows):
+    """the time of every frame; of a stream, which has no length, of as many frames as the tracking rows need"""
+    try:
+        n_frames = len(video)
+    except TypeError:
+        n_frames = int(max([r[0] for r in rows] or [0.0]) * video.frame_rate) + 2
+    return [i / video.frame_rate for i in range(n_frames)]
 
 
 def cluster(embeddings, output, threshold=0.6, force=False, metric="euclidean", ctx=None, do_not_cooccur=False):
@@ -449,9 +424,7 @@ def demo(video, tracking, output, height=400, t_from=0.0, t_until=None, shift=0.
     vw, vh = video.size
     width, height = render.demo_size(vw, vh, height)
     rate = float(video.frame_rate)
-    labels = render.read_labels(label) if isinstance(label, str) else label
-    marks = formats.read_landmarks(landmark) if isinstance(landmark, str) else landmark
-    rows = formats.read_tracks(tracking) if isinstance(tracking, str) else tracking
+    labels, marks, rows = _load(label, render.read_labels), _load(landmark, formats.read_landmarks), _load(tracking, formats.read_tracks)
     plan = render.build_plan(rows, rate, len(video), width, height, marks, labels, t_from, t_until, shift)
     return _render_plan(video, plan, output, width, height, matrix, full_range, fps if fps is not None else rate, ctx, ring_depth)
 
@@ -461,34 +434,16 @@ def _render_plan(video, plan, output, width, height, matrix, full_range, fps, ct
     one render per output frame into the egress ring (this thread) -> writer thread -> YUV4MPEG2."""
     import queue
     import threading
-    from . import render, runtime
+    from . import render
+    from .feed import FrameFeed
     by_index = {}
     for k, (i, _, _) in enumerate(plan):
         by_index.setdefault(i, []).append(k)
-    last_wanted = max(by_index) if by_index else -1
     ring = ctx.egress_ring(width, height, matrix, full_range, depth=ring_depth)
     writer = render.Y4mWriter(output, width, height, render.rate_tag(video, fps), full_range)
-    q = queue.Queue(maxsize=max(2, ring_depth))
     wq = queue.Queue()
     free = threading.Semaphore(ring_depth)             # slots the writer has given back
-    state = {"error": None}
-
-    def reader():
-        stager = runtime.HostFrameStager(ctx, ring_depth)
-        try:
-            if hasattr(video, "frame"):          # a source that can seek: only the frames the plan shows are read (--from deep into a file)
-                source = ((fi, video.frame(fi)) for fi in sorted(by_index))
-            else:
-                source = ((fi, frame) for fi, (_, frame) in enumerate(video) if fi in by_index or fi > last_wanted)
-            for fi, frame in source:
-                if fi > last_wanted or state["error"] is not None:
-                    break
-                q.put((fi,) + stager.stage(frame))
-            stager.close()
-        except BaseException as e:          # noqa: BLE001 -- re-raised below
-            state["error"] = e
-        finally:
-            q.put(None)
+    state = {"error": None}                            # the writer thread's; an error of this thread stops its writes
 
     def drain():
         try:
@@ -506,39 +461,28 @@ def _render_plan(video, plan, output, width, height, matrix, full_range, fps, ct
             while wq.get() is not None:
                 free.release()
 
-    rt = threading.Thread(target=reader, name="pvface-demo-reader")
     wt = threading.Thread(target=drain, name="pvface-demo-writer")
-    rt.start()
-    wt.start()
     try:
-        while state["error"] is None:
-            item = q.get()
-            if item is None:
-                break
-            fi, dev, owned = item
-            for k in by_index[fi]:
-                free.acquire()
-                if state["error"] is not None:
-                    free.release()
-                    break
-                wq.put(ring.submit(dev, plan[k][2]))
-            if owned:
-                dev.release()                # the kernels that read it are queued: the buffer is recycled behind them
-    except BaseException as e:              # noqa: BLE001 -- re-raised below
-        state["error"] = state["error"] or e
-    finally:
-        wq.put(None)
-        wt.join()
-        while True:                          # an error on this side: let the reader run out, and release what it had staged
+        with FrameFeed(ctx, video, by_index, ahead=ring_depth, ring_depth=ring_depth, seek=True, name="pvface-demo-reader") as feed:
+            wt.start()
             try:
-                left = q.get(timeout=0.05)
-            except queue.Empty:
-                if not rt.is_alive():
-                    break
-                continue
-            if left is not None and left[2]:
-                left[1].release()
-        rt.join()
+                for fi, dev in feed:
+                    if state["error"] is not None:
+                        break
+                    for k in by_index[fi]:
+                        free.acquire()
+                        if state["error"] is not None:
+                            free.release()
+                            break
+                        wq.put(ring.submit(dev, plan[k][2]))
+                    feed.release(dev)            # the kernels that read it are queued: the buffer is recycled behind them
+            except BaseException as e:          # noqa: BLE001 -- on its way to the caller
+                state["error"] = state["error"] or e
+                raise
+            finally:
+                wq.put(None)
+                wt.join()
+    finally:
         writer.close()
         ring.close()
     if state["error"] is not None:
@@ -557,8 +501,7 @@ def redact(video, tracking, output, height=0, t_from=0.0, t_until=None, shift=0.
     vw, vh = video.size
     width, height = (int(vw), int(vh)) if not height else render.demo_size(vw, vh, height)
     rate = float(video.frame_rate)
-    labels = render.read_labels(label) if isinstance(label, str) else label
-    rows = formats.read_tracks(tracking) if isinstance(tracking, str) else tracking
+    labels, rows = _load(label, render.read_labels), _load(tracking, formats.read_tracks)
     plan = render.build_redaction_plan(rows, rate, len(video), width, height, labels, only, keep, pad, cells, shape, mode, colour,
                                        t_from, t_until, shift)
     count = sum(len(prims) for _, _, prims in plan)
@@ -577,9 +520,8 @@ def faces(video, tracking, landmarks, output, per=4, tile=150, columns=None, lab
     asks for the quality sums of `batch` faces per library call (the chips are made and reduced on the device; 40 bytes a face come
     back).  The choice is made here (faces.py).  Pass 2 reads only the frames of the chosen faces and makes one sheet call.  Returns
     {"width", "height", "groups", "faces", "shown"}."""
-    import queue
-    import threading
     from . import faces as _faces, render, runtime
+    from .feed import FrameFeed
     ctx = ctx or runtime.default_context()
     if not (str(output) == "-" or str(output).endswith((".ppm", ".npy"))):
         raise ValueError("faces: the output is a .ppm or .npy path, or - for a PPM on stdout")
@@ -588,71 +530,28 @@ def faces(video, tracking, landmarks, output, per=4, tile=150, columns=None, lab
     if int(per) < 1:
         raise ValueError("faces: --per is at least 1")
     frame_width, frame_height = video.frame_size
-    rows = formats.read_tracks(tracking) if isinstance(tracking, str) else tracking
-    marks = formats.read_landmarks(landmarks) if isinstance(landmarks, str) else landmarks
-    labels = render.read_labels(label) if isinstance(label, str) else label
-    all_faces = _faces.landmark_faces(rows, marks, [t for t, _ in _times(video)], frame_width, frame_height)
+    rows, marks, labels = _load(tracking, formats.read_tracks), _load(landmarks, formats.read_landmarks), _load(label, render.read_labels)
+    all_faces = _faces.landmark_faces(rows, marks, _frame_times(video, rows), frame_width, frame_height)
     by_frame = {}
     for i, f in enumerate(all_faces):
         by_frame.setdefault(f[2], []).append(i)
     sums = np.zeros((len(all_faces), 5), np.int64)
 
     # ---- pass 1: the quality of every face
-    last_wanted = max(by_frame) if by_frame else -1
-    q = queue.Queue(maxsize=max(2, int(ahead)))
-    state = {"error": None}
-
-    def reader():
-        stager = runtime.HostFrameStager(ctx, 16)
-        try:
-            for fi, (t, rgb) in enumerate(video):
-                if fi > last_wanted or state["error"] is not None:
-                    break
-                if fi not in by_frame:
-                    continue
-                rgb, owned = stager.stage(rgb)
-                q.put((fi, rgb, owned))
-            stager.close()
-        except BaseException as e:          # noqa: BLE001 -- re-raised below
-            state["error"] = e
-        finally:
-            q.put(None)
-
-    th = threading.Thread(target=reader, name="pvface-faces-reader")
-    th.start()
-    try:
-        pend_f, pend_i, pend_own = [], [], []
+    with FrameFeed(ctx, video, by_frame, ahead=ahead, name="pvface-faces-reader") as feed:
+        pend_f, pend_i = [], []
 
         def flush():
             if pend_i:
                 sums[pend_i] = ctx.face_quality(pend_f, np.stack([all_faces[i][4] for i in pend_i]))
-            for f in pend_own:
-                f.release()
-            del pend_f[:], pend_i[:], pend_own[:]
-        while state["error"] is None:
-            item = q.get()
-            if item is None:
-                break
-            fi, dev, owned = item
-            if owned:
-                pend_own.append(dev)
+            feed.release_all(pend_f)
+            del pend_f[:], pend_i[:]
+        for fi, dev in feed:
             for i in by_frame[fi]:
                 pend_f.append(dev); pend_i.append(i)
             if len(pend_i) >= batch:
                 flush()
-        if state["error"] is None:
-            flush()
-    except BaseException as e:              # noqa: BLE001 -- re-raised below
-        state["error"] = state["error"] or e
-    finally:
-        while th.is_alive():                 # an error on this side: let the reader run out
-            try:
-                q.get(timeout=0.05)
-            except queue.Empty:
-                pass
-        th.join()
-    if state["error"] is not None:
-        raise state["error"]
+        flush()
 
     # ---- the choice
     sym = [_faces.symmetry(f[4]) for f in all_faces]
@@ -680,28 +579,11 @@ def faces(video, tracking, landmarks, output, per=4, tile=150, columns=None, lab
                     fx.write("%s %d " % (g[0], rank) + _faces.quality_line(all_faces[i][0], all_faces[i][1], sums[i], sym[i], sc[i], ok[i]))
 
     # ---- pass 2: the frames of the chosen faces, one sheet call
-    need = sorted(set(all_faces[i][2] for i in flat))
-    stager = runtime.HostFrameStager(ctx, max(2, min(len(need), 16)))
-    dev, own = {}, []
-    try:
-        if hasattr(video, "frame"):
-            source = ((fi, video.frame(fi)) for fi in need)
-        else:
-            wanted = set(need)
-            source = ((fi, frame) for fi, (_, frame) in enumerate(video) if fi in wanted)
-        for fi, frame in source:
-            d, owned = stager.stage(frame)
-            dev[fi] = d
-            if owned:
-                own.append(d)
-            if len(dev) == len(need):
-                break
-        stager.close()
+    need = set(all_faces[i][2] for i in flat)
+    with FrameFeed(ctx, video, need, ahead=ahead, ring_depth=max(2, min(len(need), 16)), seek=True, name="pvface-faces-reader") as feed:
+        dev = dict(feed)
         sheet = ctx.face_sheet([dev[all_faces[i][2]] for i in flat], np.stack([all_faces[i][4] for i in flat]),
                                [xy for c in corners for xy in c], int(tile), W, H, _faces.BACKGROUND, prims)
-    finally:
-        for d in own:
-            d.release()
     if str(output) == "-":
         sys.stdout.buffer.write(_faces.ppm_bytes(sheet))
         sys.stdout.buffer.flush()
@@ -721,22 +603,14 @@ def talk(video, tracking, landmarks, output, window=0.4, on=3.0, off=1.5, min_du
     A face is compared with the face of its track on the frame before; the last frame of a batch is kept alive and leads the next
     call, its faces without a predecessor and their rows discarded, so links cross batches.  The rest is talk.py.  Returns {"faces",
     "linked", "segments"}."""
-    import queue
-    import threading
     from . import faces as _faces, render, runtime, talk as _talk
+    from .feed import FrameFeed
     ctx = ctx or runtime.default_context()
     if int(batch) < 1:
         raise ValueError("talk: a batch holds at least one face")
     frame_width, frame_height = video.frame_size
-    rows = formats.read_tracks(tracking) if isinstance(tracking, str) else tracking
-    marks = formats.read_landmarks(landmarks) if isinstance(landmarks, str) else landmarks
-    labels = render.read_labels(label) if isinstance(label, str) else label
-    try:
-        n_frames = len(video)
-    except TypeError:                        # a stream: as many frame times as the tracking file needs
-        n_frames = int(max([r[0] for r in rows] or [0.0]) * video.frame_rate) + 2
-    times = [i / video.frame_rate for i in range(n_frames)]
-    all_faces = [f for f in _faces.landmark_faces(rows, marks, times, frame_width, frame_height)
+    rows, marks, labels = _load(tracking, formats.read_tracks), _load(landmarks, formats.read_landmarks), _load(label, render.read_labels)
+    all_faces = [f for f in _faces.landmark_faces(rows, marks, _frame_times(video, rows), frame_width, frame_height)
                  if f[0] >= t_from and (t_until is None or f[0] < t_until)]
     prev = _talk.link([(f[2], f[1]) for f in all_faces])
     by_frame = {}
@@ -744,77 +618,28 @@ def talk(video, tracking, landmarks, output, window=0.4, on=3.0, off=1.5, min_du
         by_frame.setdefault(f[2], []).append(i)
     out = np.full((len(all_faces), 8), -1, np.int32)
 
-    last_wanted = max(by_frame) if by_frame else -1
-    q = queue.Queue(maxsize=max(2, int(ahead)))
-    state = {"error": None}
-
-    def reader():
-        stager = runtime.HostFrameStager(ctx, 16)
-        try:
-            if last_wanted >= 0:
-                for fi, (t, rgb) in enumerate(video):
-                    if fi > last_wanted or state["error"] is not None:
-                        break
-                    if fi not in by_frame:
-                        continue
-                    rgb, owned = stager.stage(rgb)
-                    q.put((fi, rgb, owned))
-            stager.close()
-        except BaseException as e:          # noqa: BLE001 -- re-raised below
-            state["error"] = e
-        finally:
-            q.put(None)
-
-    th = threading.Thread(target=reader, name="pvface-talk-reader")
-    th.start()
-    carry = []                               # the last frame of the batch before: [(frame index, device frame, owned)]
-    try:
-        pend = []
+    with FrameFeed(ctx, video, by_frame, ahead=ahead, name="pvface-talk-reader") as feed:
+        carry, pend = [], []                 # [(frame index, device frame)]; carry: the last frame of the batch before
 
         def flush():
             frames, idx = [], []
-            for fi, dev, _ in carry + pend:
+            for fi, dev in carry + pend:
                 for i in by_frame[fi]:
                     frames.append(dev); idx.append(i)
-            lead = sum(len(by_frame[fi]) for fi, _, _ in carry)
+            lead = sum(len(by_frame[fi]) for fi, _ in carry)
             local = dict((i, k) for k, i in enumerate(idx))
             p = [-1 if k < lead else local.get(prev[i], -1) for k, i in enumerate(idx)]
             got = ctx.face_motion(frames, np.stack([all_faces[i][4] for i in idx]), p)
             out[idx[lead:]] = got[lead:]
-            for _, dev, owned in carry + pend[:-1]:
-                if owned:
-                    dev.release()
+            feed.release_all(dev for _, dev in carry + pend[:-1])
             carry[:] = pend[-1:]
             del pend[:]
-        while state["error"] is None:
-            item = q.get()
-            if item is None:
-                break
+        for item in feed:
             pend.append(item)
-            if sum(len(by_frame[fi]) for fi, _, _ in pend) >= batch:
+            if sum(len(by_frame[fi]) for fi, _ in pend) >= batch:
                 flush()
-        if state["error"] is None and pend:
+        if pend:
             flush()
-    except BaseException as e:              # noqa: BLE001 -- re-raised below
-        state["error"] = state["error"] or e
-    finally:
-        while th.is_alive():                 # an error on this side: let the reader run out
-            try:
-                item = q.get(timeout=0.05)
-                if item is not None:
-                    pend.append(item)
-            except queue.Empty:
-                pass
-        th.join()
-        while not q.empty():
-            item = q.get()
-            if item is not None:
-                pend.append(item)
-        for _, dev, owned in carry + pend:
-            if owned:
-                dev.release()
-    if state["error"] is not None:
-        raise state["error"]
 
     linked = [p >= 0 for p in prev]
     per, segs = _talk.analyse([(f[0], f[1], f[4]) for f in all_faces], out, linked, window, on, off, min_duration, max_pause, max_dark)
@@ -842,9 +667,8 @@ def tube(video, tracking, landmarks, output, size=224, region="face", scale=None
     at most `max_open` files are open at a time (tube.FilePool).  With `align` the windows follow the smoothed eye line of the landmarks
     (oriented windows, Context.frame_warps) and the index lines carry `CX CY BX BY K`.  Returns {"tubes", "pictures", "files", "open_peak"}."""
     import os
-    import queue
-    import threading
     from . import faces as _faces, pipeline, render, runtime, tube as _tube
+    from .feed import FrameFeed
     ctx = ctx or runtime.default_context()
     if fmt not in ("y4m", "npy"):
         raise ValueError("tube: the format is y4m or npy")
@@ -858,17 +682,10 @@ def tube(video, tracking, landmarks, output, size=224, region="face", scale=None
         raise ValueError("tube: a batch holds 1 .. %d pictures" % _tube.MAX_CROPS)
     size = int(size)
     frame_width, frame_height = video.frame_size
-    rows = formats.read_tracks(tracking) if isinstance(tracking, str) else tracking
-    labels = render.read_labels(label) if isinstance(label, str) else label
-    spans = _tube.read_segments(segments) if isinstance(segments, str) else segments
-    try:
-        n_frames = len(video)
-    except TypeError:                        # a stream: as many frame times as the tracking file needs
-        n_frames = int(max([r[0] for r in rows] or [0.0]) * video.frame_rate) + 2
-    times = [i / video.frame_rate for i in range(n_frames)]
+    rows, labels, spans = _load(tracking, formats.read_tracks), _load(label, render.read_labels), _load(segments, _tube.read_segments)
+    times = _frame_times(video, rows)
     if region == "mouth" or align:
-        marks = formats.read_landmarks(landmarks) if isinstance(landmarks, str) else landmarks
-        all_faces = _faces.landmark_faces(rows, marks, times, frame_width, frame_height)
+        all_faces = _faces.landmark_faces(rows, _load(landmarks, formats.read_landmarks), times, frame_width, frame_height)
     if region == "face":                     # every face of the tracking file; aligned, with its points where the landmark file has a row for it
         points = dict(((int(round(f[0] * 1000.0)), f[1]), f[4]) for f in all_faces) if align else {}
         all_faces = [(T, int(ident), fi, box, points.get((int(round(T * 1000.0)), int(ident))))
@@ -892,77 +709,32 @@ def tube(video, tracking, landmarks, output, size=224, region="face", scale=None
         if not left[ti]:
             writers.pop(ti).close()
 
-    last_wanted = max(by_frame) if by_frame else -1
-    q = queue.Queue(maxsize=max(2, int(ahead)))
-    state = {"error": None}
-
-    def reader():
-        stager = runtime.HostFrameStager(ctx, 16)
-        try:
-            if last_wanted >= 0:
-                for fi, (t, rgb) in enumerate(video):
-                    if fi > last_wanted or state["error"] is not None:
-                        break
-                    if fi not in by_frame:
-                        continue
-                    rgb, owned = stager.stage(rgb)
-                    q.put((fi, rgb, owned))
-            stager.close()
-        except BaseException as e:          # noqa: BLE001 -- re-raised below
-            state["error"] = e
-        finally:
-            q.put(None)
-
-    th = threading.Thread(target=reader, name="pvface-tube-reader")
-    th.start()
-    pend = []
     try:
-        def flush():
-            frames, jobs = [], []
-            for fi, dev, _ in pend:
-                for job in by_frame[fi]:
-                    frames.append(dev); jobs.append(job)
-            for k0 in range(0, len(jobs), int(batch)):
-                part = jobs[k0:k0 + int(batch)]
-                got = (ctx.frame_warps if align else ctx.frame_crops)(frames[k0:k0 + int(batch)], [j[2] for j in part], size, "rgb" if fmt == "npy" else "yuv420", matrix, full_range)
-                for (ti, _, _), picture in zip(part, got):
-                    write(ti, picture)
-            for _, dev, owned in pend:
-                if owned:
-                    dev.release()
-            del pend[:]
-        while state["error"] is None:
-            item = q.get()
-            if item is None:
-                break
-            pend.append(item)
-            if sum(len(by_frame[fi]) for fi, _, _ in pend) >= batch:
-                flush()
-        if state["error"] is None and pend:
-            flush()
-    except BaseException as e:              # noqa: BLE001 -- re-raised below
-        state["error"] = state["error"] or e
-    finally:
-        while th.is_alive():                 # an error on this side: let the reader run out
-            try:
-                item = q.get(timeout=0.05)
-                if item is not None:
-                    pend.append(item)
-            except queue.Empty:
-                pass
-        th.join()
-        while not q.empty():
-            item = q.get()
-            if item is not None:
+        with FrameFeed(ctx, video, by_frame, ahead=ahead, name="pvface-tube-reader") as feed:
+            pend = []                        # [(frame index, device frame)]
+
+            def flush():
+                frames, jobs = [], []
+                for fi, dev in pend:
+                    for job in by_frame[fi]:
+                        frames.append(dev); jobs.append(job)
+                for k0 in range(0, len(jobs), int(batch)):
+                    part = jobs[k0:k0 + int(batch)]
+                    got = (ctx.frame_warps if align else ctx.frame_crops)(frames[k0:k0 + int(batch)], [j[2] for j in part], size, "rgb" if fmt == "npy" else "yuv420", matrix, full_range)
+                    for (ti, _, _), picture in zip(part, got):
+                        write(ti, picture)
+                feed.release_all(dev for _, dev in pend)
+                del pend[:]
+            for item in feed:
                 pend.append(item)
-        for _, dev, owned in pend:
-            if owned:
-                dev.release()
+                if sum(len(by_frame[fi]) for fi, _ in pend) >= batch:
+                    flush()
+            if pend:
+                flush()
+    finally:
         for wr in writers.values():
             wr.close()
         pool.close()
-    if state["error"] is not None:
-        raise state["error"]
     if index:
         with open(index, "w") as fx:
             for fname, track, part in tubes:
@@ -1158,6 +930,11 @@ def main(argv=None):
         if a.range is not None:
             over["full_range"] = a.range == "full"
         return open_video(a.video, a.fps, **over)
+
+    def colours(v, matrix, rng):
+        """matrix and full_range of what a verb writes: the option, else what the video says of itself, else BT.601 limited"""
+        return dict(matrix=matrix or getattr(v, "matrix", "601"),
+                    full_range=(rng == "full") if rng is not None else bool(getattr(v, "full_range", False)))
     if a.verb == "track":
         res = track(video(), a.shot, a.tracking, detect_min_size=a.min_size, detect_every=a.every,
                     track_min_overlap_ratio=a.min_overlap, track_min_confidence=a.min_confidence, track_max_gap=a.max_gap, ctx=ctx)
@@ -1182,8 +959,7 @@ def main(argv=None):
     elif a.verb == "demo":
         v = video()
         res = demo(v, a.tracking, a.output, height=a.height, t_from=a.t_from, t_until=a.t_until, shift=a.shift, landmark=a.landmark,
-                   label=a.label, matrix=a.matrix or getattr(v, "matrix", "601"),
-                   full_range=(a.range == "full") if a.range is not None else bool(getattr(v, "full_range", False)), fps=a.fps, ctx=ctx)
+                   label=a.label, fps=a.fps, ctx=ctx, **colours(v, a.matrix, a.range))
     elif a.verb == "redact":
         if (a.only is not None or a.keep is not None) and a.label is None:
             ap.error("--only / --keep select by label: they need --label")
@@ -1191,9 +967,8 @@ def main(argv=None):
             ap.error("--cells is at least 1 and --pad at least 0")
         v = video()
         res = redact(v, a.tracking, a.output, height=a.height, t_from=a.t_from, t_until=a.t_until, shift=a.shift, label=a.label, only=a.only,
-                     keep=a.keep, pad=a.pad, cells=a.cells, shape=a.shape, mode=a.mode, colour=a.colour, draw=a.draw,
-                     matrix=a.matrix or getattr(v, "matrix", "601"),
-                     full_range=(a.range == "full") if a.range is not None else bool(getattr(v, "full_range", False)), fps=a.fps, ctx=ctx)
+                     keep=a.keep, pad=a.pad, cells=a.cells, shape=a.shape, mode=a.mode, colour=a.colour, draw=a.draw, fps=a.fps, ctx=ctx,
+                     **colours(v, a.matrix, a.range))
     elif a.verb == "faces":
         try:
             res = faces(video(), a.tracking, a.landmarks, a.output, per=a.per, tile=a.tile, columns=a.columns, label=a.label, only=a.only,
@@ -1212,12 +987,10 @@ def main(argv=None):
             ap.error("tube takes <video> <tracking> [<landmarks>] <output-directory>")
         try:
             v = video()
-            rng = a.out_range or a.range
             res = tube(v, a.tracking, a.rest[0] if len(a.rest) == 2 else None, a.rest[-1], size=a.size, region=a.region, scale=a.scale,
                        smooth=a.smooth, label=a.label, only=a.only, segments=a.segments, min_length=a.min_length, t_from=a.t_from,
-                       t_until=a.t_until, fmt=a.fmt, matrix=a.out_matrix or a.matrix or getattr(v, "matrix", "601"),
-                       full_range=(rng == "full") if rng is not None else bool(getattr(v, "full_range", False)), index=a.index, fps=a.fps, ctx=ctx,
-                       align=a.align)
+                       t_until=a.t_until, fmt=a.fmt, index=a.index, fps=a.fps, ctx=ctx, align=a.align,
+                       **colours(v, a.out_matrix or a.matrix, a.out_range or a.range))
         except (KeyError, ValueError) as e:
             ap.error(str(e.args[0]) if e.args else str(e))
     elif a.verb == "extract":

@@ -121,8 +121,11 @@ def test_extract_verb_hands_on_errors_of_its_threads(tmp_path):
     tp = str(tmp_path / "track.txt")
     formats.write_tracks(tp, make_tracks(60))
     lp, ep = str(tmp_path / "landmarks.txt"), str(tmp_path / "embedding.txt")
+    ctx = ScriptContext(fail_at=1)
     with pytest.raises(RuntimeError, match="scripted device error"):               # the computing thread
-        cli.extract(video, "unused", "unused", tp, lp, ep, ctx=ScriptContext(fail_at=1), batch=7, ahead=4)
+        cli.extract(video, "unused", "unused", tp, lp, ep, ctx=ctx, batch=7, ahead=4)
+    assert all(d.released for d in ctx.frames) and len(ctx.frames) > 0             # every staged frame went back
+    assert len(ctx.frames) <= 2 * 7 + 4 + 2                                        # the reader stopped: two calls of at most 7 frames, `ahead`, one in hand on each side
 
     class BadVideo(ScriptVideo):                                                    # the reader thread
         def __iter__(self):
@@ -130,15 +133,19 @@ def test_extract_verb_hands_on_errors_of_its_threads(tmp_path):
                 if k == 20:
                     raise IOError("scripted decode error")
                 yield item
+    ctx = ScriptContext()
     with pytest.raises(IOError, match="scripted decode error"):
-        cli.extract(BadVideo(60), "unused", "unused", tp, lp, ep, ctx=ScriptContext(), batch=7, ahead=4)
+        cli.extract(BadVideo(60), "unused", "unused", tp, lp, ep, ctx=ctx, batch=7, ahead=4)
+    assert all(d.released for d in ctx.frames) and len(ctx.frames) > 0
     orig = formats.embedding_rows                                                   # the writer thread
     try:
         def boom(*a, **k):
             raise ValueError("scripted formatter error")
         formats.embedding_rows = boom
+        ctx = ScriptContext()
         with pytest.raises(ValueError, match="scripted formatter error"):
-            cli.extract(video, "unused", "unused", tp, lp, ep, ctx=ScriptContext(), batch=7, ahead=4)
+            cli.extract(video, "unused", "unused", tp, lp, ep, ctx=ctx, batch=7, ahead=4)
+        assert all(d.released for d in ctx.frames) and len(ctx.frames) > 0
     finally:
         formats.embedding_rows = orig
 

@@ -372,6 +372,7 @@ def test_faces_verb_hands_on_errors_and_refuses(tmp_path, capsys):
     ctx = ScriptContext(fail_at=2)
     with pytest.raises(RuntimeError, match="scripted device error"):
         cli.faces(video, tp, lp, str(tmp_path / "s.ppm"), ctx=ctx, batch=5, ahead=2)
+    assert all(d.released for d in ctx.frames) and len(ctx.frames) > 0              # every frame the reader had staged was given back
     with pytest.raises(ValueError, match=r"--tile.*--per.*--only"):                 # 5 tracks x 600-pixel tiles x 30 a row: beyond 16384
         cli.faces(video, tp, lp, str(tmp_path / "s.ppm"), per=30, tile=600, ctx=ScriptContext())
     with pytest.raises(ValueError, match=r"\.ppm or \.npy"):
