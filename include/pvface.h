@@ -390,7 +390,12 @@ int32_t pvf_embed_chips_jitter(pvf_handle ctx, const uint8_t* chips, int32_t n, 
 /* ref: clustering.py:100-112  -squareform(pdist(X,'euclidean')) reduced to the T x T matrix of block means;
  * X float64 [N][dim], rows grouped by track, row_start[T+1]; D float64 [T][T] (positive distances).
  * Like the reference (clustering.py:104-112: itertools.combinations(range(n_clusters), 2), matrix[i, j] = matrix[j, i]) only the
- * track pairs i < j are computed; D[j][i] is a copy of D[i][j], the diagonal is zero. */
+ * track pairs i < j are computed; D[j][i] is a copy of D[i][j], the diagonal is zero.
+ * row_start, in every entry of this section: checked on the host before any device work (csrc/group_blocks.h, the check of the
+ * identification entries below) -- it starts at 0, is non-decreasing, has NO EMPTY TRACK and ends at N; otherwise the call returns an
+ * error and writes nothing.  The entries that take a matrix instead of rows (pvf_cluster_dist, pvf_cluster_upper and their _cooccur
+ * siblings) have no N: row_start gives them the track sizes, and the same rules hold with N = row_start[T].  The float32 entries read
+ * order[k] for every k < N: `order`, when given, holds N entries. */
 int32_t pvf_pair_mean_dist(pvf_handle ctx, const double* X, int32_t N, int32_t dim, const int32_t* row_start,
                            int32_t T, double* D);
 /* same with the pair distance chosen: metric 0 = Euclidean (the reference, clustering.py:101), 1 = cosine distance 1 - a.b / (|a| |b|)

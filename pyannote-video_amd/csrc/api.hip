@@ -1032,6 +1032,7 @@ static int32_t cluster_matrix(const std::string& name, pvf_handle h, const doubl
     API_BEGIN
     ENTER(c, h);
     PVF_REQUIRE(T > 0 && src && row_start && labels, name + ": bad arguments");
+    check_groups(name.c_str(), "row_start", row_start, T, row_start[T]);      // (a matrix entry knows the track sizes only: the table ends where it ends)
     check_cooccur(name, co, T);
     c->s_clu1.ensure(dist_matrix_bytes(T));
     double* dD = c->s_clu1.as<double>();

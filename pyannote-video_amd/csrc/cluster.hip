@@ -392,47 +392,17 @@ static void pair_mean_dist_mfma(Ctx* c, const PairInput& in, int N, const int32_
 {
     constexpr int DIM = 128;
     // ---- blocking (host, O(N)): blocks of 16 consecutive rows; segments = runs of one track inside a block
-    const int nb = (N + 15) / 16;
-    std::vector<int> row_track(N), row_segidx(N, 0), blk_cont(nb, -1), blk_clean(nb, 1), seg_track((size_t)nb * 16, -1), seg_part((size_t)nb * 16, -1);
-    std::vector<int> big_track, big_c0, big_nc, is_big(T, 0);
-    for (int t = 0; t < T; ++t) for (int r = row_start[t]; r < row_start[t + 1]; ++r) row_track[r] = t;
-    for (int b = 0; b < nb; ++b) {
-        const int r0 = b * 16, nr = std::min(16, N - r0);
-        int seg = 0;
-        for (int r = r0; r < r0 + nr; ++r) {
-            if (r > r0 && row_track[r] != row_track[r - 1]) ++seg;
-            row_segidx[r] = seg;
-            seg_track[(size_t)b * 16 + seg] = row_track[r];
-        }
-        if (r0 + nr < N && row_track[r0 + nr] == row_track[r0 + nr - 1]) blk_cont[b] = seg;      // the last segment's track goes on
-        if (b > 0 && row_track[r0] == row_track[r0 - 1]) blk_clean[b] = 0;                         // ... and this block takes it over
-    }
-    // tracks that span several blocks: one row of P per (track, block), summed in block order afterwards
-    int n_chunks = 0;
-    for (int t = 0; t < T; ++t) {
-        if (row_start[t + 1] <= row_start[t]) continue;
-        const int b_first = row_start[t] / 16, b_last = (row_start[t + 1] - 1) / 16;
-        if (b_last == b_first) continue;
-        big_track.push_back(t); big_c0.push_back(n_chunks); big_nc.push_back(b_last - b_first + 1);
-        is_big[t] = 1;
-        for (int b = b_first; b <= b_last; ++b)
-            seg_part[(size_t)b * 16 + (b == b_first ? row_segidx[row_start[t]] : 0)] = n_chunks++;
-    }
+    const Blocking bl(row_start, T, N);
+    const int nb = bl.nb, n_chunks = bl.n_parts;
+    const std::vector<int>&row_track = bl.row_group, &row_segidx = bl.segidx, &blk_cont = bl.blk_cont, &seg_track = bl.seg_group, &seg_part = bl.seg_part;
+    const std::vector<int>&big_track = bl.big_group, &big_c0 = bl.big_c0, &big_nc = bl.big_nc, &is_big = bl.is_big;
     // column ranges, cut only at blocks that do not take a segment over from their predecessor (the sums of a track that spans blocks
     // are carried from tile to tile inside a range).  With the upper triangle about half of the (row group, range) workgroups have work
     // (the ones on the diagonal part of a range); ~24 pieces per workgroup slot (3 resident per CU) keep the tail of the launch -- the
-    // last pieces running alone -- near 2 % of it; a piece is at least 16 column blocks (its row blocks are loaded once per piece)
+    // last pieces running alone -- near 2 % of it; a piece is at least 16 column blocks (its row blocks are loaded once per piece).
+    // (a range is addressed with 32-bit byte offsets: at most 2^20 rows, hence the floor on the number of ranges)
     const int row_groups = (nb + 3) / 4;
-    int want_ranges = (2 * 24 * 3 * c->n_cu + row_groups - 1) / row_groups;
-    want_ranges = std::max(1, std::min(want_ranges, std::max(1, nb / 16)));
-    want_ranges = std::max(want_ranges, (nb >> 16) + 1);            // a range is addressed with 32-bit byte offsets: at most 2^20 rows
-    std::vector<int> range_b0{0};
-    for (int k = 1; k < want_ranges; ++k) {
-        int b = (int)((long long)nb * k / want_ranges);
-        while (b < nb && !blk_clean[b]) ++b;
-        if (b > range_b0.back() && b < nb) range_b0.push_back(b);
-    }
-    range_b0.push_back(nb);
+    const std::vector<int> range_b0 = cut_ranges(bl, (2 * 24 * 3 * c->n_cu + row_groups - 1) / row_groups, (nb >> 16) + 1);
     const int n_ranges = (int)range_b0.size() - 1;
     for (int k = 0; k < n_ranges; ++k) PVF_REQUIRE(range_b0[k + 1] - range_b0[k] <= (1 << 17), "pair_mean_dist: a track of more than a million rows");
     // ---- device buffers
@@ -499,7 +469,7 @@ void pair_mean_dist_dev(Ctx* c, const PairInput& in, int N, int dim, const int32
     if (t1 < 0) t1 = T;
     PVF_REQUIRE(0 <= t0 && t0 <= t1 && t1 <= T, "pair_mean_dist: bad track range");
     PVF_REQUIRE(N > 0 && T > 0 && dim > 0 && dim <= 4096, "pair_mean_dist: bad sizes");
-    PVF_REQUIRE(row_start[0] == 0 && row_start[T] == N, "pair_mean_dist: row_start must cover [0, N)");
+    check_groups("pair_mean_dist", "row_start", row_start, T, N);
     PVF_REQUIRE(metric == 0 || metric == 1, "pair_mean_dist: metric 0 (euclidean) or 1 (cosine)");
     PVF_REQUIRE(!mirror || (t0 == 0 && t1 == T), "pair_mean_dist: only a whole matrix can be mirrored");
     PVF_REQUIRE((in.X != nullptr) != (in.emb != nullptr), "pair_mean_dist: one input table");

@@ -297,54 +297,6 @@ __global__ void __launch_bounds__(256) identify_pick_k(const double* __restrict_
     }
 }
 
-namespace {
-// 16-row blocks of one table whose rows are sorted by group: segments = runs of rows of one group inside a block (cluster.hip's blocking)
-struct Blocking {
-    int nb = 0, n_parts = 0;
-    std::vector<int> segidx, blk_cont, blk_clean, seg_group, seg_part, big_group, big_c0, big_nc, is_big;
-    Blocking(const int32_t* start, int n_groups, int n_rows)
-    {
-        nb = (n_rows + 15) / 16;
-        std::vector<int> row_group(n_rows);
-        segidx.assign(n_rows, 0); blk_cont.assign(nb, -1); blk_clean.assign(nb, 1);
-        seg_group.assign((size_t)nb * 16, -1); seg_part.assign((size_t)nb * 16, -1); is_big.assign(n_groups, 0);
-        for (int t = 0; t < n_groups; ++t) for (int r = start[t]; r < start[t + 1]; ++r) row_group[r] = t;
-        for (int b = 0; b < nb; ++b) {
-            const int r0 = b * 16, nr = std::min(16, n_rows - r0);
-            int seg = 0;
-            for (int r = r0; r < r0 + nr; ++r) {
-                if (r > r0 && row_group[r] != row_group[r - 1]) ++seg;
-                segidx[r] = seg;
-                seg_group[(size_t)b * 16 + seg] = row_group[r];
-            }
-            if (r0 + nr < n_rows && row_group[r0 + nr] == row_group[r0 + nr - 1]) blk_cont[b] = seg;     // the last segment's group goes on
-            if (b > 0 && row_group[r0] == row_group[r0 - 1]) blk_clean[b] = 0;                            // ... and this block takes it over
-        }
-        // groups that span several blocks: one part per (group, block), summed in block order afterwards
-        for (int t = 0; t < n_groups; ++t) {
-            const int b_first = start[t] / 16, b_last = (start[t + 1] - 1) / 16;
-            if (b_last == b_first) continue;
-            big_group.push_back(t); big_c0.push_back(n_parts); big_nc.push_back(b_last - b_first + 1);
-            is_big[t] = 1;
-            for (int b = b_first; b <= b_last; ++b) seg_part[(size_t)b * 16 + (b == b_first ? segidx[start[t]] : 0)] = n_parts++;
-        }
-    }
-};
-
-void check_groups(const char* who, const char* what, const int32_t* start, int n_groups, int n_rows)
-{
-    const std::string p = std::string(who) + ": " + what;
-    PVF_REQUIRE(start != nullptr, p + " is NULL");
-    PVF_REQUIRE(start[0] == 0, p + " must start at 0");
-    for (int t = 0; t < n_groups; ++t) {
-        PVF_REQUIRE(start[t + 1] >= start[t], p + " must be non-decreasing");
-        PVF_REQUIRE(start[t + 1] > start[t], p + " holds an empty group");
-    }
-    PVF_REQUIRE(start[n_groups] == n_rows, p + " must end at the number of rows");
-}
-
-} // namespace
-
 // every check of a distance call, on the host, before any device work
 void identify_check_dist(const char* who, int N, const int32_t* row_start, int T, int M, const int32_t* gal_start, int K, int dim, int metric)
 {
@@ -375,16 +327,8 @@ double* gallery_mean_dist_dev(Ctx* c, const double* X, int N, const int32_t* row
     // identity that spans blocks are carried from tile to tile inside a range).  Every (query row group, range) workgroup has work: ~24
     // pieces per workgroup slot (3 resident per CU) as in K10, a piece at least 16 column blocks (its query blocks are loaded once per piece)
     const int row_groups = (q.nb + 3) / 4;
-    int want_ranges = (24 * 3 * c->n_cu + row_groups - 1) / row_groups;
-    want_ranges = std::max(1, std::min(want_ranges, std::max(1, g.nb / 16)));
-    want_ranges = std::max(want_ranges, (g.nb >> 15) + 1);          // a range is addressed with 32-bit byte offsets: at most 2^20 rows
-    std::vector<int> range_b0{0};
-    for (int k = 1; k < want_ranges; ++k) {
-        int b = (int)((long long)g.nb * k / want_ranges);
-        while (b < g.nb && !g.blk_clean[b]) ++b;
-        if (b > range_b0.back() && b < g.nb) range_b0.push_back(b);
-    }
-    range_b0.push_back(g.nb);
+    // (a range is addressed with 32-bit byte offsets: at most 2^20 rows, hence the floor on the number of ranges)
+    const std::vector<int> range_b0 = cut_ranges(g, (24 * 3 * c->n_cu + row_groups - 1) / row_groups, (g.nb >> 15) + 1);
     const int n_ranges = (int)range_b0.size() - 1;
     for (int k = 0; k < n_ranges; ++k)
         PVF_REQUIRE(range_b0[k + 1] - range_b0[k] <= (1 << 16), "identify: an identity of more than a million rows (32-bit byte offsets)");

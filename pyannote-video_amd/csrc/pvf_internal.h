@@ -16,6 +16,7 @@
 #include "../../include/pvface.h"
 #include "scratch_layout.h"      // PvfError, ScratchLayout
 #include "chip_plan.h"           // ChipJob, ChipDetails, chip_plan_geom
+#include "group_blocks.h"        // check_groups, Blocking, cut_ranges
 
 #define PVF_FHOG_STRIDE 32
 

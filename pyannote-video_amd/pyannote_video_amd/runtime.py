@@ -1106,13 +1106,28 @@ class Context(object):
             a = np.ascontiguousarray(a, np.float32).reshape(-1, 128)
         return ptr(a), int(a.strides[0]) if len(a) else 512, len(a), 0, a
 
+    @staticmethod
+    def _f32_order(name, order, rs, n_src):
+        """`order` as int32, after the checks the library cannot make (it reads order[k] for every k < row_start[-1])"""
+        if rs.ndim != 1 or len(rs) < 2:
+            raise ValueError("%s: row_start holds T + 1 entries, T >= 1" % name)
+        N = int(rs[-1])
+        if order is None:
+            if n_src < N:
+                raise ValueError("%s: %d rows, row_start ends at %d" % (name, n_src, N))
+            return None
+        order = np.ascontiguousarray(order, np.int32)
+        if order.ndim != 1 or len(order) != N:
+            raise ValueError("%s: `order` holds %d entries, row_start ends at %d" % (name, order.size, N))
+        return order
+
     def _cluster_tracks_f32(self, emb, order, row_start, threshold, decimals=5, metric=0, extent=None, flags=0):
         """the in-memory clustering (pvf_cluster_tracks_f32): float32 descriptors (numpy [n, 128] or DeviceRows), rows of the table =
         round(emb[order], decimals) made on the device, upper-triangle pair means, mirror, agglomeration -> (labels, merge log)"""
         p, stride, n_src, on_dev, keep = self._f32_rows(emb)
         rs = np.ascontiguousarray(row_start, np.int32)
         T = len(rs) - 1
-        order = None if order is None else np.ascontiguousarray(order, np.int32)
+        order = self._f32_order("cluster_tracks_f32", order, rs, n_src)
         N = int(rs[-1])
         labels = np.zeros(T, np.int32)
         log = np.zeros((max(T - 1, 1), 4), np.float64)
@@ -1139,7 +1154,7 @@ class Context(object):
         p, stride, n_src, on_dev, keep = self._f32_rows(emb)
         rs = np.ascontiguousarray(row_start, np.int32)
         T = len(rs) - 1
-        order = None if order is None else np.ascontiguousarray(order, np.int32)
+        order = self._f32_order("pair_upper_rows_f32", order, rs, n_src)
         m = int(track1) - int(track0)
         if out is None:
             res = np.zeros((max(m, 0), T), np.float64)
@@ -1192,6 +1207,8 @@ class Context(object):
         X = np.ascontiguousarray(X, np.float64)
         rs = np.ascontiguousarray(row_start, np.int32)
         T = len(rs) - 1
+        if X.ndim != 2 or rs.ndim != 1 or T < 1 or X.shape[0] < int(rs[-1]):
+            raise ValueError("pair rows: X [N, dim] with N = row_start[-1] = %s rows is expected, got %s" % (rs[-1] if rs.size else None, X.shape))
         D = np.zeros((T, T), np.float64)
         check(fn(self._h, ptr(X), X.shape[0], X.shape[1], ptr(rs), T, int(track0), int(track1), ptr(D)))
         return D

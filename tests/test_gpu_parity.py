@@ -348,7 +348,10 @@ def _tracks(rng, sizes, K=40, noise=0.05):
 
 def test_pair_mean_dist_matrix_core_kernel_all_block_shapes(ctx, oracle):
     """K10 on the f64 matrix cores: tracks shorter than / equal to / longer than a 16-row block, packed and chunked, identical and
-    near-identical rows (the Gram form's cancellation zone), against the oracle's direct double loop"""
+    near-identical rows (the Gram form's cancellation zone), against the oracle's direct double loop.  N = 501 is 32 blocks and two
+    column ranges are wanted, but the 250-row track covers every block from the proposed cut to the end, so this table is planned as ONE
+    range (tests/test_cluster_cases.py asserts that): the range cuts, and shares on and around them, are in
+    tests/test_gpu_cluster_layouts.py"""
     rng = np.random.default_rng(11)
     sizes = np.array([1, 1, 1, 15, 16, 17, 2, 3, 31, 32, 33, 1, 5, 5, 5, 1, 64, 7, 9, 250, 1, 1], np.int64)
     X, rs, _ = _tracks(rng, sizes)
