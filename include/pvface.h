@@ -525,6 +525,29 @@ int32_t pvf_identify(pvf_handle ctx, const double* X, int32_t N, const int32_t* 
                      const int32_t* gal_start, int32_t K, int32_t dim, int32_t metric, double threshold, int32_t* best, double* best_dist,
                      int32_t* second, double* second_dist, double* D /* T x K host, or NULL */);
 
+/* ---- search: the exact k nearest rows of a table (SEARCH.md) ------------------------------------------------------------------------
+ * WHERE ELSE a face appears: for every query row of Qrows float64 [Q][dim] the k nearest rows of X float64 [N][dim], the table: the rows
+ * of one or many embedding files.  There is NO REFERENCE CALL.  Euclidean only, and EXACT: the rules are stated in integers.
+ *   quantisation  q(v) = rint(v * 100000.0), the product in float64, ties to even: the integer a 5-decimal value stands for.  A table or
+ *              a query holding a value that is not finite, or with |q| > 2^20 (|v| above about 10.48), is REFUSED as a whole; the message
+ *              names the row and column of the first such value in row-major order.  Nothing is clamped, and no result is computed.
+ *   distance   d2(a, b) = sum over c of (q(a_c) - q(b_c))^2, an exact integer in [0, 2^49].  sqrt(d2) / 1e5 is what people read; it is
+ *              never compared.
+ *   hits of a query: the rows i that are not excluded and, with a cut, have d2 <= max_d2 (-1: no cut), ordered by (d2, i) ascending; the
+ *              first k are kept.  The order is total, so the result is unique: the same bits whatever the chunking and the device.
+ *   exclusion  with row_group int32 [N] and query_group int32 [Q] (both, or both NULL): row i is skipped for query q when
+ *              row_group[i] == query_group[q] >= 0 -- a query taken from a track of the table does not find its own track.
+ *   outputs    count[q] = min(k, number of hits); idx int32 [Q][k] and d2 int64 [Q][k], both -1 past count[q].
+ * Checked on the host before any device work: dim == 128; Q, N >= 1; 1 <= k <= 1024 (a k above N is legal: the tail is -1);
+ * N <= 2^30; max_d2 >= -1; the two group arrays together.  The table is streamed through HBM in chunks of rows (PVF_SEARCH_CHUNK, read
+ * at every call, sets the rows per chunk: the test switch); Q x N is never written anywhere: device memory is O(chunk + Q k ranges).
+ * pvf_search_plan (host only): how a call of these sizes is cut -- out = {rows per chunk, chunks, column ranges per chunk, 16-row blocks
+ * per range, entries of a query's pending region, bytes of the selection arena}. */
+int32_t pvf_search(pvf_handle ctx, const double* Qrows, int32_t Q, const double* X, int64_t N, int32_t dim, int32_t k,
+                   int64_t max_d2, const int32_t* query_group, const int32_t* row_group,
+                   int32_t* idx /* Q x k */, int64_t* d2 /* Q x k */, int32_t* count /* Q */);
+int32_t pvf_search_plan(int32_t Q, int64_t N, int32_t k, int64_t out[6]);
+
 /* ---- file formats (host) ------------------------------------------------------------------------------ */
 /* ref: scripts/pyannote-face.py:299-311  the lines of landmarks.txt / embedding.txt: "{t:.3f} {identifier:d}" + n_cols x " {v:.<decimals>f}"
  * + newline per row, byte for byte what Python's format writes (both are the correctly rounded decimal).  values [n_rows][n_cols];

@@ -9,6 +9,8 @@
     python -m pyannote_video_amd enroll  [--append] <video> <landmark_model> <embedding_model> <name> <gallery>
     python -m pyannote_video_amd enroll-track [--append] <embeddings> <track> <name> <gallery>
     python -m pyannote_video_amd identify [--threshold 0.6] [--metric euclidean|cosine] [--labels PATH] [--unknown NAME] [--scores PATH] <embeddings> <gallery> <output>
+    python -m pyannote_video_amd search  [-k 100] [--max-distance D] [--rows] [--include-self] (--gallery PATH --name NAME | --from EMBEDDINGS --track ID)
+                                         <output> <embeddings> [<embeddings> ...]
     python -m pyannote_video_amd demo    [--height 400] [--from 0] [--until T] [--shift 0] [--landmark PATH] [--label PATH] <video> <tracking> <output>
     python -m pyannote_video_amd redact  [--height 0] [--from 0] [--until T] [--shift 0] [--label PATH] [--only A,B | --keep A,B] [--pad 25] [--cells 8]
                                          [--shape ellipse|box] [--mode mosaic|smooth|fill] [--colour r,g,b] [--draw] <video> <tracking> <output>
@@ -23,6 +25,8 @@ embedding.txt: formats.py).  `cluster` is the verb BASELINE.json's north_star na
 only (face/clustering.py:130-134).  It writes `identifier label` lines, the file `demo --label` reads (pyannote-face.py:87,391-397).
 `enroll` / `enroll-track` / `identify` (identification.py; no reference verb) name tracks or clusters against a gallery of enrolled faces:
 `identify` writes `identifier name` lines, the same file `demo --label` reads; `process --gallery` does it in the same run.
+`search` (search.py; no reference verb; SEARCH.md) answers "where else does this face appear?": the exact k nearest faces of one or more
+embedding files to a track or to a person of a gallery, one `rank distance path track T` line per hit, nearest first.
 `demo` (pyannote-face.py:317-413) writes the video with the tracks, their numbers and labels and, with --landmark, the nose lines drawn
 on it, as a YUV4MPEG2 stream: to a `.y4m` path, or to stdout for `-` (`... demo film.y4m track.txt - | ffmpeg -i - out.mp4`).  Resize,
 drawing and RGB -> YUV 4:2:0 run in one kernel on the GPU (DEMO.md states every pixel; the font is the project's own, not OpenCV's
@@ -336,6 +340,33 @@ def identify(embeddings, gallery, output, threshold=0.6, metric="euclidean", lab
     identification.write_identification(output, result, np.unique(track).tolist(), label, unknown, per_cluster=labels is not None,
                                         scores_output=scores)
     return {g: (name if matched else None, bd, second, sd) for g, name, bd, second, sd, matched in result}
+
+
+def search(output, embeddings, k=100, max_distance=None, rows=False, include_self=False, gallery=None, name=None, source=None, track=None,
+           ctx=None):
+    """The k nearest faces of the embedding files to a query -- the rows of a person of a gallery (`gallery`, `name`) or of a track of an
+    embedding file (`source`, `track`) -- as `rank distance path track T` lines, nearest first (`output`: a path, or - for stdout).
+    Without `rows` only the best hit of each (file, track) among the k is kept: the tracks that own the k nearest faces.  A query taken
+    from a track of a searched file does not find its own track, unless `include_self`.  -> the hits"""
+    from . import search as _search
+    if (gallery is None) == (source is None) or (gallery is not None and name is None) or (source is not None and track is None):
+        raise ValueError("search: the query is --gallery PATH --name NAME, or --from EMBEDDINGS --track ID")
+    if not 1 <= int(k) <= _search.MAX_K:
+        raise ValueError("search: k must lie in 1 .. %d" % _search.MAX_K)
+    fs = _search.FaceSearch(ctx=ctx)
+    for path in embeddings:
+        fs.add(path)
+    if len(fs) == 0:
+        raise ValueError("search: the table is empty (no row in %s)" % ", ".join(embeddings))
+    own = -1
+    if gallery is not None:
+        query = fs.rows_of_person(gallery, name)
+    else:
+        query = fs.rows_of_track(source, track)
+        own = -1 if include_self else fs.group_of(source, track)
+    hits = fs.search(query, k=k, max_distance=max_distance, exclude_group=own, collapse=not rows)
+    _search.write_hits(output, hits)
+    return hits
 
 
 def enroll_track(embeddings, track, name, gallery, append=False):
@@ -822,6 +853,16 @@ def _parser():
     en.add_argument("--jitters", type=int, default=0, help="descriptors averaged over this many jittered face chips (dlib's num_jitters; "
                     "0 or 1: the plain descriptor)")
     en.add_argument("--jitter-seed", type=int, default=0, help="seed of the jitter transforms (they depend on the seed and the jitter's index alone)")
+    se = sub.add_parser("search", help="the exact k nearest faces of one or more embedding files to a track or to a person of a gallery")
+    se.add_argument("output", help="a path, or - for stdout: `rank distance path track T` lines, nearest first")
+    se.add_argument("embeddings", nargs="+", help="the embedding files that are searched")
+    se.add_argument("-k", type=int, default=100, help="faces kept (1 .. 1024)")
+    se.add_argument("--max-distance", type=float, default=None, help="no face further than this (0.6: the same person, by the embedder's convention)")
+    se.add_argument("--rows", action="store_true", help="every one of the k faces, not the best of each (file, track) among them")
+    se.add_argument("--include-self", action="store_true", help="with --from: the query's own track may be found")
+    se.add_argument("--gallery", default=None); se.add_argument("--name", default=None)
+    se.add_argument("--from", dest="source", default=None, help="the embedding file the query track is taken from")
+    se.add_argument("--track", type=int, default=None)
     et = sub.add_parser("enroll-track", help="the rows of one track of an embedding file, under a name, into a gallery file")
     et.add_argument("embeddings"); et.add_argument("track", type=int); et.add_argument("name"); et.add_argument("gallery")
     et.add_argument("--append", action="store_true")
@@ -952,6 +993,12 @@ def main(argv=None):
                      jitter_seed=a.jitter_seed)
     elif a.verb == "enroll-track":
         enroll_track(a.embeddings, a.track, a.name, a.gallery, append=a.append)
+    elif a.verb == "search":
+        try:
+            search(a.output, a.embeddings, k=a.k, max_distance=a.max_distance, rows=a.rows, include_self=a.include_self, gallery=a.gallery,
+                   name=a.name, source=a.source, track=a.track, ctx=ctx)
+        except ValueError as e:
+            ap.error(str(e))
     elif a.verb == "shot":
         shot(video(), a.output, height=a.height, window=a.window, threshold=a.threshold, ctx=ctx)
     elif a.verb == "thread":

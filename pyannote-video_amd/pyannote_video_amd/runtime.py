@@ -1064,6 +1064,35 @@ class Context(object):
                                    *([ptr(o) for o in out] + [None if D is None else ptr(D)])))
         return out + (D,) if return_dist else out
 
+    # ---- search: the exact k nearest rows of a table (pvf_search; SEARCH.md states the rules in integers)
+    def search(self, Qrows, X, k, max_d2=-1, query_group=None, row_group=None):
+        """-> (idx int32 [Q, k], d2 int64 [Q, k], count int32 [Q]): per query row the k nearest rows of X by (d2, index), -1 past count"""
+        Qrows = np.ascontiguousarray(Qrows, np.float64)
+        X = np.ascontiguousarray(X, np.float64)
+        if Qrows.ndim != 2 or X.ndim != 2 or Qrows.shape[1] != X.shape[1]:
+            raise ValueError("search: Qrows [Q, dim] and X [N, dim] are expected")
+        if (query_group is None) != (row_group is None):
+            raise ValueError("search: query_group and row_group are given together or not at all")
+        qg = rg = None
+        if query_group is not None:
+            qg = np.ascontiguousarray(query_group, np.int32)
+            rg = np.ascontiguousarray(row_group, np.int32)
+            if qg.shape != (Qrows.shape[0],) or rg.shape != (X.shape[0],):
+                raise ValueError("search: one query_group per query row and one row_group per table row")
+        Q, k = Qrows.shape[0], int(k)
+        kk = min(max(k, 0), 1024)                      # (a k out of range is refused by the library, before it writes anything)
+        idx, d2, count = np.full((Q, kk), -1, np.int32), np.full((Q, kk), -1, np.int64), np.zeros(Q, np.int32)
+        check(self._l.pvf_search(self._h, ptr(Qrows), Q, ptr(X), X.shape[0], X.shape[1], k, int(max_d2), ptr(qg), ptr(rg), ptr(idx), ptr(d2),
+                                 ptr(count)))
+        return idx, d2, count
+
+    @staticmethod
+    def search_plan(Q, N, k):
+        """how pvf_search cuts a call of these sizes -> dict(chunk_rows, n_chunks, n_ranges, range_blocks, pending, arena_bytes)"""
+        out = np.zeros(6, np.int64)
+        check(_lib.lib().pvf_search_plan(int(Q), int(N), int(k), ptr(out)))
+        return dict(zip(("chunk_rows", "n_chunks", "n_ranges", "range_blocks", "pending", "arena_bytes"), (int(v) for v in out)))
+
     # The four agglomerating calls have a `_cooccur` sibling that takes `extent` (float64 [T, 2]: start and end of every track, seconds):
     # the do-not-cooccur constraint (clustering.py:142-143; pvf_cluster_*_cooccur) -- tracks whose extents intersect never share a
     # cluster.  They return (labels, merge log, n_blocked = the co-occurring pairs); `flags` bit 0 is the library's test switch
