@@ -356,6 +356,31 @@ int32_t pvf_frame_crops(pvf_handle ctx, const pvf_handle* frames, const int32_t*
 int32_t pvf_frame_warps(pvf_handle ctx, const pvf_handle* frames, const int32_t* windows /* n*5 */, int32_t n, int32_t S, int32_t flags,
                         uint8_t* out, int32_t out_on_device);
 
+/* ---- the storyboard verb (STORYBOARD.md): whole frames as small pictures, and the sheet of them -----------------------------------*/
+#define PVF_THUMB_MAX_SIDE 1024          /* tw and th of a thumbnail */
+#define PVF_THUMB_MAX_FRAMES 65536       /* frames of one pvf_frame_thumbs call */
+/* n RGB pictures [th][tw][3], tight and in call order: picture i is the whole of frame frames[i], all frames of one size (h, w), as the
+ * exact area average.  With x in units of 1 / tw source pixel, source column j is [j tw, (j + 1) tw), output column X is [X w, (X + 1) w)
+ * and wx(X, j) the length they share (sum over j: w); rows the same with th, h and wy (sum: h);
+ *   pixel(Y, X, c) = (sum_i sum_j wy(Y, i) wx(X, j) byte(i, j, c) + (w h) // 2) // (w h)
+ * in 64-bit integers.  One rule for every ratio on either axis: tw = w, th = h is the frame byte for byte, an integer reduction the mean
+ * rounded half up, an integer enlargement replication.  out: host memory, or device memory with out_on_device = 1; the call is complete
+ * when it returns.  Pictures go through the device in rounds (32 MiB of them, or the pictures the environment variable PVF_THUMB_ROUND
+ * names, read at the call), a round's copy to the host running under the next round's kernel; nothing depends on the rounds.  n = 0
+ * does nothing.  Refused before any work: n < 0 or beyond PVF_THUMB_MAX_FRAMES, null pointers with n > 0, tw or th outside
+ * 1 .. PVF_THUMB_MAX_SIDE, flags other than 0, an unknown or released frame, frames of different sizes. */
+int32_t pvf_frame_thumbs(pvf_handle ctx, const pvf_handle* frames, int32_t n, int32_t tw, int32_t th, int32_t flags,
+                         uint8_t* out /* n*th*tw*3 */, int32_t out_on_device);
+/* pvf_chip_sheet with rectangular tiles that are copied, not resampled: the sheet [H][W][3] (host) is filled with the background
+ * (r | g << 8 | b << 16); thumbnail i of `thumbs` (host, [n][th][tw][3]) sits with its top-left corner at (xy[2 i], xy[2 i + 1]) -- any
+ * int32, clipped to the sheet, the tile of the highest index that covers a pixel wins, whatever the rounds (PVF_THUMB_ROUND tiles, or
+ * 32 MiB of them); then the RECT / LINE / TEXT primitives in list order over the tiles, drawn as the renderer draws them.  n = 0 gives
+ * background and primitives.  Refused: pvf_chip_sheet's reasons (PVF_SHEET_MAX_*, PVF_RENDER_MAX_*, a redaction or an unknown
+ * primitive, a text run outside the pool, null pointers), and tw or th outside 1 .. PVF_THUMB_MAX_SIDE. */
+int32_t pvf_thumb_sheet(pvf_handle ctx, const uint8_t* thumbs /* n*th*tw*3 */, int32_t n, const int32_t* xy /* n*2 */, int32_t tw, int32_t th,
+                        int32_t W, int32_t H, uint32_t background, const pvf_prim* prims, int32_t n_prims, const uint8_t* text,
+                        int64_t text_bytes, uint8_t* rgb /* H*W*3 */);
+
 /* ---- num_jitters (JITTER.md) ------------------------------------------------------------------------
  * dlib: compute_face_descriptor(img, shape, num_jitters) -- the descriptor is the fp32 mean of the network's outputs on J = num_jitters
  * perturbed copies of the aligned chip (shift, zoom, rotation, mirror).  The transform of jitter j is a function of (seed, j) alone,

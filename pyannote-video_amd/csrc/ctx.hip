@@ -356,6 +356,7 @@ extern "C" int32_t pvf_ctx_destroy(pvf_handle h)
     ingest_free_all(c);
     render_free_all(c);
     tube_free_all(c);
+    board_free_all(c);
     for (auto& kv : c->frame_pool) for (auto q : kv.second) {
         if (q.free_after) (void)hipEventDestroy(q.free_after);
         if (q.free_after_det) (void)hipEventDestroy(q.free_after_det);

@@ -300,13 +300,9 @@ static void quality_run(Ctx* c, const ChipSource& src, int n, int64_t* out, cons
     HIP_CHECK(hipStreamSynchronize(c->stream));
 }
 
-static void sheet_run(Ctx* c, const ChipSource& src, int n, const int32_t* xy, int S, int W, int H, uint32_t background, const pvf_prim* prims,
-                      int n_prims, const uint8_t* text, int64_t text_bytes, uint8_t* rgb, const char* who)
+void sheet_check(const std::string& w, int W, int H, uint32_t background, const pvf_prim* prims, int n_prims, const uint8_t* text,
+                 int64_t text_bytes, const uint8_t* rgb)
 {
-    const std::string w(who);
-    check_source(src, n, w);
-    PVF_REQUIRE(n == 0 || xy, w + ": null tile corners");
-    PVF_REQUIRE(S >= PVF_SHEET_MIN_TILE && S <= PVF_SHEET_MAX_TILE, w + ": tile side outside PVF_SHEET_MIN_TILE .. PVF_SHEET_MAX_TILE");
     PVF_REQUIRE(W >= 1 && H >= 1 && W <= PVF_SHEET_MAX_SIDE && H <= PVF_SHEET_MAX_SIDE, w + ": sheet side outside 1 .. PVF_SHEET_MAX_SIDE");
     PVF_REQUIRE((int64_t)W * H <= PVF_SHEET_MAX_PIXELS, w + ": more sheet pixels than PVF_SHEET_MAX_PIXELS");
     PVF_REQUIRE(rgb, w + ": null output");
@@ -324,6 +320,26 @@ static void sheet_run(Ctx* c, const ChipSource& src, int n, const int32_t* xy, i
         PVF_REQUIRE(p.c >= 0 && (int64_t)p.c + p.d <= text_bytes, w + ": a text run outside the text pool");
         PVF_REQUIRE(p.scale >= 1 && p.scale <= PVF_RENDER_MAX_SCALE, w + ": text scale outside 1 .. PVF_RENDER_MAX_SCALE");
     }
+}
+
+void sheet_prims_launch(Ctx* c, const pvf_prim* d_prims, int n_prims, const uint8_t* d_text, int W, int H, uint8_t* d_rgb)
+{
+    if (!n_prims) return;
+    SheetPrimArgs a;
+    a.prims = d_prims; a.n = n_prims; a.text = d_text; a.W = W; a.H = H; a.rgb = d_rgb;
+    ProfScope prof(c, "sheet");
+    hipLaunchKernelGGL(sheet_prims_k, dim3((W + SH_TW - 1) / SH_TW, (H + SH_TH - 1) / SH_TH), dim3(256), 0, c->stream, a);
+    HIP_CHECK(hipGetLastError());
+}
+
+static void sheet_run(Ctx* c, const ChipSource& src, int n, const int32_t* xy, int S, int W, int H, uint32_t background, const pvf_prim* prims,
+                      int n_prims, const uint8_t* text, int64_t text_bytes, uint8_t* rgb, const char* who)
+{
+    const std::string w(who);
+    check_source(src, n, w);
+    PVF_REQUIRE(n == 0 || xy, w + ": null tile corners");
+    PVF_REQUIRE(S >= PVF_SHEET_MIN_TILE && S <= PVF_SHEET_MAX_TILE, w + ": tile side outside PVF_SHEET_MIN_TILE .. PVF_SHEET_MAX_TILE");
+    sheet_check(w, W, H, background, prims, n_prims, text, text_bytes, rgb);
     ScratchLayout chips_lay, lay;
     const auto sChips = chips_lay.take<uint8_t>((size_t)std::min(n, Q_ROUND) * Q_BYTES);
     const auto sRgb = lay.take<uint8_t>((size_t)W * H * 3);
@@ -347,13 +363,7 @@ static void sheet_run(Ctx* c, const ChipSource& src, int n, const int32_t* xy, i
         hipLaunchKernelGGL(sheet_tiles_k, grid, dim3(256), 0, c->stream, a);
         HIP_CHECK(hipGetLastError());
     }
-    if (n_prims) {
-        SheetPrimArgs a;
-        a.prims = sPrims.in(c->s_act0); a.n = n_prims; a.text = sText.in(c->s_act0); a.W = W; a.H = H; a.rgb = sRgb.in(c->s_act0);
-        ProfScope prof(c, "sheet");
-        hipLaunchKernelGGL(sheet_prims_k, grid, dim3(256), 0, c->stream, a);
-        HIP_CHECK(hipGetLastError());
-    }
+    sheet_prims_launch(c, sPrims.in(c->s_act0), n_prims, sText.in(c->s_act0), W, H, sRgb.in(c->s_act0));
     HIP_CHECK(hipMemcpyAsync(rgb, sRgb.in(c->s_act0), sRgb.bytes(), hipMemcpyDeviceToHost, c->stream));
     HIP_CHECK(hipStreamSynchronize(c->stream));
 }

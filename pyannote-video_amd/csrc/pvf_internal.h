@@ -270,6 +270,7 @@ struct Ctx {
     void* ingest_rings = nullptr;                          // pinned staging rings of this context (ingest.hip)
     void* render_state = nullptr;                          // what the demo renderer keeps per context (render.hip)
     void* tube_state = nullptr;                            // what pvf_frame_crops keeps per context (tube.hip)
+    void* board_state = nullptr;                           // what pvf_frame_thumbs keeps per context (board.hip)
     struct MlPlanCache* ml_plans = nullptr;   // detector launch plans of this context (detect.hip); freed by ml_plans_free
     std::map<std::vector<int>, std::unique_ptr<DevBuf>> resize_tabs;   // pvf_frame_resize coefficient tables by (in_w, in_h, out_w, out_h)
     const void* feat_ring_owner = nullptr;    // plan whose zero padding ring s_feat currently holds
@@ -368,6 +369,7 @@ struct ResizeTab { std::vector<int32_t> idx; std::vector<int16_t> coef; };
 ResizeTab linear_table(int in, int out);
 void render_free_all(Ctx* c);            // render.hip: resize tables, scratch and egress rings of the context
 void tube_free_all(Ctx* c);              // tube.hip: output buffers, copy stream and events of pvf_frame_crops
+void board_free_all(Ctx* c);             // board.hip: the same of pvf_frame_thumbs
 void det_nms(const DetectorModel& m, const std::vector<RawDet>& sorted, std::vector<RawDet>& out);
 void det_pyramid_level(Ctx* c, const Frame& f, int upsample, int level, std::vector<uint8_t>* out, int* h, int* w);
 void det_level_features(Ctx* c, const Frame& f, int upsample, int level, std::vector<float>* out, int* fh, int* fw);
@@ -406,6 +408,11 @@ struct ChipSource { const uint8_t* host; const pvf_handle* frames; const int32_t
 const EmbedModel& faces_geometry();
 void faces_make_chips(Ctx* c, const pvf_handle* frames, const int32_t* pts, int m, uint8_t* d_chips);
 void faces_source_round(Ctx* c, const ChipSource& src, int i0, int m, uint8_t* d_chips);       // chips [i0, i0 + m) of the source, on c->stream
+// what every sheet call checks of its picture and its primitive list (host, before any device work), and sheet_prims_k over a sheet that
+// is already on the device (prims: 256-byte aligned device memory), on c->stream -- shared with board.hip's pvf_thumb_sheet
+void sheet_check(const std::string& w, int W, int H, uint32_t background, const pvf_prim* prims, int n_prims, const uint8_t* text,
+                 int64_t text_bytes, const uint8_t* rgb);
+void sheet_prims_launch(Ctx* c, const pvf_prim* d_prims, int n_prims, const uint8_t* d_text, int W, int H, uint8_t* d_rgb);
 // a layer's weights on the device as the convolution kernels read them: w [cout][cin][k][k] -> d_w ([cout][K padded to 32], k = (r, s, c)
 // with the 3-channel layer's fourth all-zero channel), w_exp, and bias / gamma / beta; conv_layer_free releases everything the layer holds
 void conv_layer_upload(ConvLayer& L, const float* w, const float* bias, const float* gamma, const float* beta);

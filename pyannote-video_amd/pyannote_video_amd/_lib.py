@@ -103,6 +103,8 @@ _SIGS = {
     "pvf_face_motion": (C.c_int32, [H, P, P, C.c_int32, P, P]),
     # the tube verb (TUBE.md): square windows of resident frames as S x S pictures
     "pvf_frame_crops": (C.c_int32, [H, P, P, C.c_int32, C.c_int32, C.c_int32, P, C.c_int32]),
+    "pvf_frame_thumbs": (C.c_int32, [H, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P, C.c_int32]),
+    "pvf_thumb_sheet": (C.c_int32, [H, P, C.c_int32, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, P, C.c_int32, P, C.c_int64, P]),
     # tube --align: oriented windows (CX, CY, BX, BY, K) of resident frames as S x S pictures
     "pvf_frame_warps": (C.c_int32, [H, P, P, C.c_int32, C.c_int32, C.c_int32, P, C.c_int32]),
     # num_jitters (JITTER.md): compute_face_descriptor(img, shape, num_jitters)

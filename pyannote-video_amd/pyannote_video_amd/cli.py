@@ -6,6 +6,9 @@
     python -m pyannote_video_amd process [options] <video> <shot.json> <landmark_model> <embedding_model> <tracking> <landmarks> <embeddings>
     python -m pyannote_video_amd shot    [options] <video> <output.json>
     python -m pyannote_video_amd thread  [--min-match 20] [--lookahead 24] <video> <shot.json> <output.json>
+    python -m pyannote_video_amd scene   <video> <thread.json> <output.json>
+    python -m pyannote_video_amd storyboard [--per 1] [--width 160] [--columns C] [--thread PATH] [--by time|thread] [--from 0] [--until T]
+                                         [--index PATH] [--batch 64] <video> <shot.json> <output>
     python -m pyannote_video_amd enroll  [--append] <video> <landmark_model> <embedding_model> <name> <gallery>
     python -m pyannote_video_amd enroll-track [--append] <embeddings> <track> <name> <gallery>
     python -m pyannote_video_amd identify [--threshold 0.6] [--metric euclidean|cosine] [--labels PATH] [--unknown NAME] [--scores PATH] <embeddings> <gallery> <output>
@@ -40,6 +43,11 @@ GPU, a sharpness and exposure reduction over every face chip of the film; the sh
 `talk` (no reference verb; TALK.md) writes one line per face with how much its mouth moved since the frame before -- displaced absolute
 differences of the aligned chip's mouth window, less those of a control window above it, computed on the GPU -- and, with --segments,
 the spans in which a track is taken to be talking: a stated rule with untuned thresholds on top of the per-face columns.
+
+`storyboard` (no reference verb; STORYBOARD.md) writes the shots of `shot` as a contact sheet -- a few frames of every shot, whole, as
+thumbnails under the shot's number and start, coloured and with --by thread lined up by the threads of `thread` -- as a binary PPM or a
+`.npy` array: what is shot 212, and is thread C one camera set-up?  The thumbnails are exact area averages made on the GPU.
+`scene` (pyannote-structure.py scene, which the reference leaves unimplemented) writes the scenes of a thread file.
 
 <video>: no codec is linked (reference video.py:345-406 runs ffmpeg); the verbs read what a decoder writes --
   * a YUV4MPEG2 file (`.y4m`, or any file that starts with `YUV4MPEG2`): 8-bit 4:2:0 / 4:2:2 / 4:4:4, memory mapped, frame rate from
@@ -443,6 +451,54 @@ def thread(video, shot, output, min_match=20, lookahead=24, ctx=None):
     return threads
 
 
+def scene(video, thread, output):
+    """Scenes (scripts/pyannote-structure.py:39 usage; its body raises NotImplementedError): the threads of `thread` with every
+    biconnected component of three or more shots relabelled (structure.thread_scenes).  The video is not opened: scenes are a function
+    of the threads alone."""
+    from .structure import thread_scenes
+    from ._core import Annotation
+    with open(thread) as fp:
+        threads = Annotation.from_json(json.load(fp))
+    scenes = thread_scenes(threads)
+    with open(output, 'w') as fp:
+        json.dump(scenes.for_json(), fp)
+    return scenes
+
+
+def storyboard(video, shot, output, per=1, width=160, columns=None, thread=None, by="time", t_from=0.0, t_until=None, index=None,
+               batch=64, ctx=None):
+    """The shots of a film as a contact sheet (STORYBOARD.md): `per` frames of every shot, whole, as thumbnails `width` pixels wide under
+    a caption, coloured by thread with `thread` (what `thread` or `scene` wrote).  The frames are read by one seeking FrameFeed and
+    reduced on the device `batch` at a time (storyboard.build).  Returns {"width", "height", "shots", "tiles"}."""
+    from . import storyboard as _board, faces as _faces, runtime
+    from ._core import Annotation
+    if not (str(output) == "-" or str(output).endswith((".ppm", ".npy"))):
+        raise ValueError("storyboard: the output is a .ppm or .npy path, or - for a PPM on stdout")
+    shots = load_shots(shot) if isinstance(shot, str) else list(shot)
+    annotation = None
+    if thread is not None:
+        if isinstance(thread, str):
+            with open(thread) as fp:
+                annotation = Annotation.from_json(json.load(fp))
+        else:
+            annotation = thread
+    ctx = ctx or runtime.default_context()
+    sheet, lines, res = _board.build(ctx, video, shots, _board.shot_labels(shots, annotation), per=per, width=width, columns=columns, by=by,
+                                     t_from=t_from, t_until=t_until, batch=batch)
+    if index:
+        with open(index, "w") as fx:
+            fx.write("".join(lines))
+    if str(output) == "-":
+        sys.stdout.buffer.write(_faces.ppm_bytes(sheet))
+        sys.stdout.buffer.flush()
+    elif str(output).endswith(".npy"):
+        np.save(output, sheet)
+    else:
+        with open(output, "wb") as fo:
+            fo.write(_faces.ppm_bytes(sheet))
+    return res
+
+
 def demo(video, tracking, output, height=400, t_from=0.0, t_until=None, shift=0.0, landmark=None, label=None, matrix="601",
          full_range=False, fps=None, ctx=None, ring_depth=16):
     """Annotated video (pyannote-face.py:317-413) as YUV4MPEG2, to a path or to stdout (`-`).  What is drawn on which frame is planned
@@ -832,6 +888,19 @@ def _parser():
     th.add_argument("video"); th.add_argument("shot"); th.add_argument("output")
     th.add_argument("--min-match", type=int, default=20)
     th.add_argument("--lookahead", type=int, default=24)
+    sc = sub.add_parser("scene", help="scenes from shot threads (pyannote-structure.py scene); the video is not opened")
+    sc.add_argument("video"); sc.add_argument("thread"); sc.add_argument("output")
+    sb = sub.add_parser("storyboard", help="the shots of a film as a contact sheet of thumbnails, as PPM or .npy")
+    sb.add_argument("video"); sb.add_argument("shot"); sb.add_argument("output", help="a .ppm or .npy path, or - for a PPM on stdout")
+    sb.add_argument("--per", type=int, default=1, choices=range(1, 9), metavar="1..8", help="frames shown per shot")
+    sb.add_argument("--width", type=int, default=160, help="width of a thumbnail, 1 .. 1024; the height keeps the frame's aspect")
+    sb.add_argument("--columns", type=int, default=None, help="shots per row (default: as many as 1920 pixels hold)")
+    sb.add_argument("--thread", default=None, help="what `thread` or `scene` wrote: captions and outlines coloured by thread")
+    sb.add_argument("--by", choices=("time", "thread"), default="time", help="shot order, or every thread on rows of its own")
+    sb.add_argument("--from", dest="t_from", type=float, default=0.0, help="shots that start at or after this, seconds")
+    sb.add_argument("--until", dest="t_until", type=float, default=None, help="shots that start before this, seconds")
+    sb.add_argument("--index", default=None, help="write `shot k frame time x y label` per tile")
+    sb.add_argument("--batch", type=int, default=64, help="frames reduced per library call, and resident at a time")
     c = sub.add_parser("cluster")
     c.add_argument("embeddings"); c.add_argument("labels")
     c.add_argument("--threshold", type=float, default=0.6)
@@ -1003,6 +1072,16 @@ def main(argv=None):
         shot(video(), a.output, height=a.height, window=a.window, threshold=a.threshold, ctx=ctx)
     elif a.verb == "thread":
         thread(video(), a.shot, a.output, min_match=a.min_match, lookahead=a.lookahead, ctx=ctx)
+    elif a.verb == "scene":
+        scene(a.video, a.thread, a.output)
+    elif a.verb == "storyboard":
+        if a.width < 1 or a.width > 1024 or a.batch < 1 or (a.columns is not None and a.columns < 1):
+            ap.error("--width is 1 .. 1024, --batch and --columns at least 1")
+        try:
+            res = storyboard(video(), a.shot, a.output, per=a.per, width=a.width, columns=a.columns, thread=a.thread, by=a.by, t_from=a.t_from,
+                             t_until=a.t_until, index=a.index, batch=a.batch, ctx=ctx)
+        except ValueError as e:
+            ap.error(str(e))
     elif a.verb == "demo":
         v = video()
         res = demo(v, a.tracking, a.output, height=a.height, t_from=a.t_from, t_until=a.t_until, shift=a.shift, landmark=a.landmark,

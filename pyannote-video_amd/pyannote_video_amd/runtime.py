@@ -857,6 +857,29 @@ class Context(object):
                                          ptr(p), len(p), ptr(text), len(text), ptr(out)))
         return out
 
+    # ---- the storyboard verb (STORYBOARD.md)
+    def frame_thumbs(self, frames, tw, th, out_ptr=None):
+        """resident frames of one size, whole, as tw x th pictures (pvf_frame_thumbs: the exact area average): uint8 [n, th, tw, 3].
+        With out_ptr, a device address that holds as much, the pictures stay in HBM and nothing is returned."""
+        n, tw, th = len(frames), int(tw), int(th)
+        out = None if out_ptr is not None else np.empty((n, th, tw, 3) if 0 < tw <= 1024 and 0 < th <= 1024 else (n, 0), np.uint8)
+        with self._staging():
+            check(self._l.pvf_frame_thumbs(self._h, ptr(self._handles(frames)), n, tw, th, 0,
+                                           C.c_void_p(int(out_ptr)) if out_ptr is not None else ptr(out), 1 if out_ptr is not None else 0))
+        return out
+
+    def thumb_sheet(self, thumbs, xy, width, height, background=(0, 0, 0), prims=()):
+        """uint8 [height, width, 3]: the thumbnails uint8 [n, th, tw, 3] copied to the corners xy (later over earlier), the primitives
+        over them (pvf_thumb_sheet; STORYBOARD.md "Sheet")"""
+        thumbs = np.ascontiguousarray(thumbs, np.uint8)
+        if thumbs.ndim != 4 or thumbs.shape[3] != 3:
+            raise ValueError("thumbnails are uint8 [n, th, tw, 3]")
+        xy, bg, p, text = self._sheet_args(len(thumbs), xy, background, prims)
+        out = self._sheet_out(width, height)
+        check(self._l.pvf_thumb_sheet(self._h, ptr(thumbs), len(thumbs), ptr(xy), int(thumbs.shape[2]), int(thumbs.shape[1]), int(width),
+                                      int(height), bg, ptr(p), len(p), ptr(text), len(text), ptr(out)))
+        return out
+
     def embed_chips(self, chips, num_jitters=0, seed=0):
         chips = np.ascontiguousarray(chips, np.uint8).reshape(-1, 150, 150, 3)
         out = np.zeros((len(chips), 128), np.float32)
