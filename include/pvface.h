@@ -573,6 +573,30 @@ int32_t pvf_search(pvf_handle ctx, const double* Qrows, int32_t Q, const double*
                    int32_t* idx /* Q x k */, int64_t* d2 /* Q x k */, int32_t* count /* Q */);
 int32_t pvf_search_plan(int32_t Q, int64_t N, int32_t k, int64_t out[6]);
 
+/* ---- footage shared between films (REPEAT.md; no reference call) -----------------------------------------------------------------
+ * A print of a frame is four uint64: H, V, SY | RANGE << 32 and a word for the caller.  With G the 9 x 9 thumbnail of the whole frame
+ * (pvf_frame_thumbs' exact area average, tw = th = 9; a side below 9 replicates) and Y[r][c] = (77 R + 150 G + 29 B + 128) >> 8 of it:
+ * bit 8 r + c of H is Y[r][c] < Y[r][c + 1], of V is Y[r][c] < Y[r + 1][c] (r, c in 0 .. 7), SY is the sum of the 81 Y, RANGE their
+ * max - min.  pvf_frame_prints writes the prints of n resident frames, of any sizes, in call order: out uint64 [n][4] in host memory, or
+ * in device memory with out_on_device = 1; the fourth word is written as 0.  n = 0 does nothing.  Refused before any work: n < 0 or
+ * beyond PVF_PRINT_MAX_ROWS, null pointers with n > 0, an unknown or released frame.
+ *
+ * pvf_print_runs: rows a of A and b of B (uint64 [N][2]: H, V) match when usable_a[a] and usable_b[b] are non-zero and
+ * popcount(Ha ^ Hb) + popcount(Va ^ Vb) <= tau.  A run (i, j, len) is a maximal sequence of matching pairs (i + t, j + t), t < len.
+ * Every run with len >= min_len is reported, ordered by (j - i, i).  B == NULL is self mode: B is A (usable_b and NB are not read) and
+ * only the diagonals j - i >= min_gap exist.  *found is always the exact number of runs; runs int32 [cap][3] holds them, sorted, when
+ * found <= cap, and is unspecified otherwise (call again with a larger cap).  NA = 0 or NB = 0 finds nothing.  Refused before any
+ * work: NA or NB outside 0 .. PVF_PRINT_MAX_ROWS, tau outside 0 .. 128, min_len < 1, self mode with min_gap < 1, cap < 0, null found,
+ * null pointers where a count is positive.  PVF_RUNS_STRIP: the rows of A a workgroup of the kernel walks (what the tests' seams are
+ * derived from). */
+#define PVF_PRINT_MAX_ROWS 16777216      /* frames of one pvf_frame_prints call; rows of a table of pvf_print_runs */
+#define PVF_RUNS_STRIP 1024
+int32_t pvf_frame_prints(pvf_handle ctx, const pvf_handle* frames, int32_t n, uint64_t* out /* n*4 */, int32_t out_on_device);
+int32_t pvf_print_runs(pvf_handle ctx, const uint64_t* A /* NA*2: H, V */, const uint8_t* usable_a, int32_t NA,
+                       const uint64_t* B, const uint8_t* usable_b, int32_t NB,   /* B == NULL: self mode */
+                       int32_t tau, int32_t min_len, int32_t min_gap,
+                       int32_t* runs /* cap*3 */, int64_t cap, int64_t* found);
+
 /* ---- file formats (host) ------------------------------------------------------------------------------ */
 /* ref: scripts/pyannote-face.py:299-311  the lines of landmarks.txt / embedding.txt: "{t:.3f} {identifier:d}" + n_cols x " {v:.<decimals>f}"
  * + newline per row, byte for byte what Python's format writes (both are the correctly rounded decimal).  values [n_rows][n_cols];

@@ -22,6 +22,9 @@
                                          <video> <tracking> <landmarks> <output>
     python -m pyannote_video_amd talk    [--window 0.4] [--on 3.0] [--off 1.5] [--min-duration 0.3] [--max-pause 0.3] [--max-dark 0.25]
                                          [--from 0] [--until T] [--label PATH] [--segments PATH] <video> <tracking> <landmarks> <output>
+    python -m pyannote_video_amd fingerprint [--from 0] [--until T] [--batch 64] <video> <prints.npy>
+    python -m pyannote_video_amd repeat  [--max-bits 10] [--flat 16] [--min-duration 2.0] [--max-gap 0.5] [--min-separation 5.0]
+                                         <output.json> <prints.npy> [<prints.npy> ...]
 
 `track` and `extract` take the reference's arguments and options and write byte-compatible files (track.txt, landmarks.txt,
 embedding.txt: formats.py).  `cluster` is the verb BASELINE.json's north_star names; the reference offers clustering through the API
@@ -48,12 +51,15 @@ the spans in which a track is taken to be talking: a stated rule with untuned th
 thumbnails under the shot's number and start, coloured and with --by thread lined up by the threads of `thread` -- as a binary PPM or a
 `.npy` array: what is shot 212, and is thread C one camera set-up?  The thumbnails are exact area averages made on the GPU.
 `scene` (pyannote-structure.py scene, which the reference leaves unimplemented) writes the scenes of a thread file.
+`fingerprint` (no reference verb; REPEAT.md) writes a 128-bit print of every frame, made on the GPU from the frame's 9 x 9 thumbnail, as a
+uint64 [n][4] `.npy`; `repeat` compares print files with themselves and with each other and writes the stretches they share -- a recap,
+the titles, a rerun -- as JSON.  The thresholds are untuned; the runs and segments are the product.
 
 <video>: no codec is linked (reference video.py:345-406 runs ffmpeg); the verbs read what a decoder writes --
   * a YUV4MPEG2 file (`.y4m`, or any file that starts with `YUV4MPEG2`): 8-bit 4:2:0 / 4:2:2 / 4:4:4, memory mapped, frame rate from
     its header (`ffmpeg -i film.mkv -pix_fmt yuv420p -f yuv4mpegpipe film.y4m`); the planes go to the GPU as they are and are
     converted to RGB there (--matrix 601|709, --range limited|full override the header);
-  * `-`: the same stream from stdin, for the verbs that read the video once and need no length (`track`, `process`, `talk`):
+  * `-`: the same stream from stdin, for the verbs that read the video once and need no length (`track`, `process`, `talk`, `fingerprint`):
     `ffmpeg -i film.mkv -pix_fmt yuv420p -f yuv4mpegpipe - | python -m pyannote_video_amd process - ...`;
   * a `.npy` file holding uint8 [N, H, W, 3] RGB frames (memory mapped; frame rate from --fps);
   * the bench's synthetic clip: `synthetic:<width>x<height>x<frames>[:shots[:faces[:seed]]]`.
@@ -499,6 +505,72 @@ def storyboard(video, shot, output, per=1, width=160, columns=None, thread=None,
     return res
 
 
+def fingerprint(video, output, t_from=0.0, t_until=None, batch=64, ctx=None, ahead=96):
+    """A print of every frame of the video whose time lies in [t_from, t_until) (REPEAT.md): one streaming pass, a reader thread pushes
+    the frames through the pinned ingest ring (RGB or YUV), this thread asks for the prints of `batch` resident frames per library call
+    (32 bytes a frame come back) and releases them.  Writes uint64 [n][4] -- H, V, SY | RANGE << 32, ms(T) | frame index << 32 -- as
+    a .npy file (`output` may be an open binary file).  Returns {"frames", "first"}."""
+    from . import repeat as _repeat, runtime
+    from .feed import FrameFeed
+    if int(batch) < 1:
+        raise ValueError("fingerprint: a batch holds at least one frame")
+    rate = float(video.frame_rate)
+    first = 0
+    while first / rate < t_from:
+        first += 1
+    end = None
+    if t_until is not None:
+        end = first
+        while end / rate < t_until:
+            end += 1
+    try:
+        end = len(video) if end is None else min(end, len(video))
+    except TypeError:                        # a stream: as far as it goes
+        pass
+    ctx = ctx or runtime.default_context()
+    parts, pend = [], []
+    with FrameFeed(ctx, video, _repeat.EveryFrame(first, end), ahead=max(ahead, 2 * int(batch)), name="pvface-fingerprint-reader") as feed:
+        def flush():
+            parts.append(ctx.frame_prints(pend))
+            feed.release_all(pend)
+            del pend[:]
+        for _, dev in feed:
+            pend.append(dev)
+            if len(pend) >= batch:
+                flush()
+        if pend:
+            flush()
+    prints = _repeat.stamp(np.concatenate(parts) if parts else np.zeros((0, 4), np.uint64), first, rate)
+    if hasattr(output, "write"):
+        np.save(output, prints)
+    else:
+        with open(output, "wb") as fo:
+            np.save(fo, prints)
+    return {"frames": int(len(prints)), "first": first}
+
+
+def repeat(output, prints, max_bits=10, flat=16, min_duration=2.0, max_gap=0.5, min_separation=5.0, ctx=None):
+    """The stretches print files share with themselves and with each other (REPEAT.md): every file against itself, beyond
+    `min_separation` seconds, and against every later one; the runs of matching prints come from the device (Context.print_runs), the
+    rest is repeat.py.  Writes a JSON list of {a, b, a_start, a_end, b_start, b_end, frames, offset} and returns it."""
+    from . import repeat as _repeat, runtime
+    if not prints:
+        raise ValueError("repeat: no print files")
+    if not 0 <= int(max_bits) <= 128:
+        raise ValueError("repeat: --max-bits is 0 .. 128")
+    files = [(str(p), _repeat.load(p)) for p in prints]
+    found = _repeat.compare(ctx or runtime.default_context(), files, max_bits=max_bits, flat=flat, min_duration=min_duration, max_gap=max_gap,
+                            min_separation=min_separation)
+    text = json.dumps(found, indent=1)
+    if str(output) == "-":
+        sys.stdout.write(text + "\n")
+        sys.stdout.flush()
+    else:
+        with open(output, "w") as fo:
+            fo.write(text + "\n")
+    return found
+
+
 def demo(video, tracking, output, height=400, t_from=0.0, t_until=None, shift=0.0, landmark=None, label=None, matrix="601",
          full_range=False, fps=None, ctx=None, ring_depth=16):
     """Annotated video (pyannote-face.py:317-413) as YUV4MPEG2, to a path or to stdout (`-`).  What is drawn on which frame is planned
@@ -901,6 +973,19 @@ def _parser():
     sb.add_argument("--until", dest="t_until", type=float, default=None, help="shots that start before this, seconds")
     sb.add_argument("--index", default=None, help="write `shot k frame time x y label` per tile")
     sb.add_argument("--batch", type=int, default=64, help="frames reduced per library call, and resident at a time")
+    fp = sub.add_parser("fingerprint", help="a 128-bit print of every frame of a video, as a uint64 [n][4] .npy file")
+    fp.add_argument("video"); fp.add_argument("output", help="the .npy path the prints are written to")
+    fp.add_argument("--from", dest="t_from", type=float, default=0.0, help="frames at or after this, seconds")
+    fp.add_argument("--until", dest="t_until", type=float, default=None, help="frames before this, seconds")
+    fp.add_argument("--batch", type=int, default=64, help="frames reduced per library call, and resident at a time")
+    rp = sub.add_parser("repeat", help="the stretches print files of `fingerprint` share with themselves and with each other, as JSON")
+    rp.add_argument("output", help="a path, or - for stdout")
+    rp.add_argument("prints", nargs="+", help="print files; each is compared with itself and with every later one")
+    rp.add_argument("--max-bits", type=int, default=10, help="bits of 128 in which two frames may differ and still match (0 .. 128)")
+    rp.add_argument("--flat", type=int, default=16, help="a frame whose 9 x 9 luma spans less than this matches nothing (black, fades)")
+    rp.add_argument("--min-duration", type=float, default=2.0, help="segments shorter than this are dropped, seconds")
+    rp.add_argument("--max-gap", type=float, default=0.5, help="runs of one offset this close are one segment, seconds")
+    rp.add_argument("--min-separation", type=float, default=5.0, help="within one file: only footage at least this far apart, seconds")
     c = sub.add_parser("cluster")
     c.add_argument("embeddings"); c.add_argument("labels")
     c.add_argument("--threshold", type=float, default=0.6)
@@ -1032,7 +1117,7 @@ def main(argv=None):
         if a.video == "-" and a.verb == "faces":
             ap.error("faces reads the video twice, once for the quality of every face and once for the frames of the chosen ones: "
                      "give it a file, not a stream on stdin")
-        if a.video == "-" and a.verb not in ("track", "process", "talk", "tube"):
+        if a.video == "-" and a.verb not in ("track", "process", "talk", "tube", "fingerprint"):
             ap.error("%s needs the length of the video: give it a file, not a stream on stdin" % a.verb)
         over = {}
         if a.matrix is not None:
@@ -1080,6 +1165,18 @@ def main(argv=None):
         try:
             res = storyboard(video(), a.shot, a.output, per=a.per, width=a.width, columns=a.columns, thread=a.thread, by=a.by, t_from=a.t_from,
                              t_until=a.t_until, index=a.index, batch=a.batch, ctx=ctx)
+        except ValueError as e:
+            ap.error(str(e))
+    elif a.verb == "fingerprint":
+        if a.batch < 1:
+            ap.error("--batch is at least 1")
+        res = fingerprint(video(), a.output, t_from=a.t_from, t_until=a.t_until, batch=a.batch, ctx=ctx)
+    elif a.verb == "repeat":
+        if not 0 <= a.max_bits <= 128:
+            ap.error("--max-bits is 0 .. 128")
+        try:
+            repeat(a.output, a.prints, max_bits=a.max_bits, flat=a.flat, min_duration=a.min_duration, max_gap=a.max_gap,
+                   min_separation=a.min_separation, ctx=ctx)
         except ValueError as e:
             ap.error(str(e))
     elif a.verb == "demo":

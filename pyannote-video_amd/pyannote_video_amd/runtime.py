@@ -1116,6 +1116,44 @@ class Context(object):
         check(_lib.lib().pvf_search_plan(int(Q), int(N), int(k), ptr(out)))
         return dict(zip(("chunk_rows", "n_chunks", "n_ranges", "range_blocks", "pending", "arena_bytes"), (int(v) for v in out)))
 
+    # ---- the fingerprint and repeat verbs (REPEAT.md)
+    def frame_prints(self, frames, out_ptr=None):
+        """resident frames, of any sizes, as prints (pvf_frame_prints): uint64 [n, 4] = H, V, SY | RANGE << 32, 0.  With out_ptr, a
+        device address that holds as much, the prints stay in HBM and nothing is returned."""
+        n = len(frames)
+        out = None if out_ptr is not None else np.zeros((n, 4), np.uint64)
+        with self._staging():
+            check(self._l.pvf_frame_prints(self._h, ptr(self._handles(frames)), n, C.c_void_p(int(out_ptr)) if out_ptr is not None else ptr(out),
+                                           1 if out_ptr is not None else 0))
+        return out
+
+    RUNS_FIRST_CAP = 65536
+
+    def print_runs(self, A, usable_a, B=None, usable_b=None, tau=10, min_len=1, min_gap=1, cap=None):
+        """-> int32 [found, 3]: the runs (i, j, len) of matching prints of A uint64 [NA, 2 or 4] against B, or against A itself from
+        diagonal min_gap on when B is None, ordered by (j - i, i) (pvf_print_runs).  The call is made again with room for every run when
+        the first cap (65 536 runs) is too small."""
+        def table(P, u, what):
+            P = np.asarray(P)
+            if P.dtype != np.uint64 or P.ndim != 2 or P.shape[1] not in (2, 4):
+                raise ValueError("print_runs: %s is uint64 [n, 2] or [n, 4]" % what)
+            u = np.ascontiguousarray(u, np.uint8)
+            if u.shape != (len(P),):
+                raise ValueError("print_runs: one usable byte per row of %s" % what)
+            return np.ascontiguousarray(P[:, :2]), u
+        A, ua = table(A, usable_a, "A")
+        if B is not None:
+            B, ub = table(B, usable_b, "B")
+        cap = self.RUNS_FIRST_CAP if cap is None else int(cap)
+        found = C.c_int64(0)
+        while True:
+            runs = np.zeros((max(cap, 0), 3), np.int32)
+            check(self._l.pvf_print_runs(self._h, ptr(A), ptr(ua), len(A), ptr(B) if B is not None else None, ptr(ub) if B is not None else None,
+                                         len(B) if B is not None else 0, int(tau), int(min_len), int(min_gap), ptr(runs), cap, C.byref(found)))
+            if found.value <= cap:
+                return runs[:found.value]
+            cap = found.value
+
     # The four agglomerating calls have a `_cooccur` sibling that takes `extent` (float64 [T, 2]: start and end of every track, seconds):
     # the do-not-cooccur constraint (clustering.py:142-143; pvf_cluster_*_cooccur) -- tracks whose extents intersect never share a
     # cluster.  They return (labels, merge log, n_blocked = the co-occurring pairs); `flags` bit 0 is the library's test switch
