@@ -534,7 +534,10 @@ int32_t pvf_pair_upper_rows_f32(pvf_handle ctx, const float* emb, int64_t row_st
  *   D[t][k]  = mean over the rows i of group t and the rows j of identity k of dist(x_i, g_j), float64, T x K row-major, computed on the
  *              f64 matrix cores by the rectangular form of K10; neither N x M nor N x K is materialised.  Defined up to rounding
  *              (rtol 1e-12 Euclidean, 1e-10 cosine), not bit for bit: the additions that form an entry depend on where the rows of the
- *              group and of the identity fall in their 16-row blocks.  The same call returns the same bits.
+ *              group and of the identity fall in their 16-row blocks.  The same call returns the same bits.  Euclidean pairs with
+ *              d^2 < 1e-3 (|x_i|^2 + |g_j|^2) are summed from their differences (identical rows: exactly 0); the others take
+ *              |x|^2 + |g|^2 - 2 x.g, whose relative error in d, C 2^-53 (|x|^2 + |g|^2) / d^2 with C <= 4.5 measured, is at most 5e-13
+ *              there, at any scale of the rows.  pvf_pair_mean_dist* (K10) computes the pairs of 128-D rows the same way.
  *   decision per group t: an entry is TAKEN when it is below +inf (NaN and +inf entries are never taken).  best = the index of the first
  *              minimum of row t among the taken entries (the lowest k wins on equal values); second = the first minimum over k != best.
  *              A row with nothing to take gives (-1, +inf); with K = 1 the second is (-1, +inf).  Then best = -1 unless

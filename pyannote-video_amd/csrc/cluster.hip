@@ -225,15 +225,17 @@ __device__ __forceinline__ void pair_tiles_body(const PtArgs& a)
                 for (int r = 0; r < 4; ++r) {
                     const double sum = na4[r] + nb;
                     d2[r] = sum - 2.0 * acc[r];
-                    // the Gram form cancels for close rows: its absolute error in d is ~1e-16 (|a|^2 + |b|^2) / d, i.e. below 1e-13 down
-                    // to d ~ 3e-3 |x|; closer pairs (identical or near-identical rows) take the differences instead
-                    fix = fix || (d2[r] < 1e-5 * sum && k4 + 4 * r < anr && colSeg[buf][i16] >= 0);
+                    // the Gram form cancels for close rows: with rho = d^2 / (|a|^2 + |b|^2) its relative error in d is C 2^-53 / rho, C up
+                    // to 4.5 measured (3.7e-11 at rho = 1e-5, 3.8e-13 at 1e-3, at |x| = 0.55 as at |x| = 9; the absolute error grows with
+                    // |x|).  Pairs below GRAM_SWITCH (1e-3: d below ~4.5e-2 |x|) take the differences instead: identical and near-identical
+                    // rows, and at the embedder's scale (|x| 6 to 12) the neighbouring frames of one track
+                    fix = fix || (d2[r] < GRAM_SWITCH * sum && k4 + 4 * r < anr && colSeg[buf][i16] >= 0);
                 }
-                if (__builtin_amdgcn_ballot_w64(fix) != 0) {           // rare: some lane of the wave holds such a pair
+                if (__builtin_amdgcn_ballot_w64(fix) != 0) {           // some lane of the wave holds such a pair
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int row = k4 + 4 * r;
-                        if (d2[r] < 1e-5 * (na4[r] + nb) && row < anr && colSeg[buf][i16] >= 0) {
+                        if (d2[r] < GRAM_SWITCH * (na4[r] + nb) && row < anr && colSeg[buf][i16] >= 0) {
                             const double* xa = a.X + (size_t)(ar0 + row) * DIM;
                             const double* xb = a.X + (size_t)(br0 + i16) * DIM;
                             double e = 0.0;

@@ -149,15 +149,16 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))
                 for (int r = 0; r < 4; ++r) {
                     const double sum = na4[r] + nb;
                     d2[r] = sum - 2.0 * acc[r];
-                    // the Gram form cancels for close rows (absolute error in d ~1e-16 (|a|^2 + |b|^2) / d): pairs closer than ~3e-3 |x|
-                    // -- a query row that is a copy of an enrolled one -- take the differences instead
-                    fix = fix || (d2[r] < 1e-5 * sum && k4 + 4 * r < anr && colSeg[buf][i16] >= 0);
+                    // the Gram form cancels for close rows (relative error in d: C 2^-53 (|a|^2 + |b|^2) / d^2, C up to 4.5 measured, as in
+                    // pair_tiles_k): pairs below GRAM_SWITCH (1e-3: closer than ~4.5e-2 |x|) -- a query row that is a copy of an enrolled
+                    // one, or a neighbouring frame of it -- take the differences instead
+                    fix = fix || (d2[r] < GRAM_SWITCH * sum && k4 + 4 * r < anr && colSeg[buf][i16] >= 0);
                 }
                 if (__builtin_amdgcn_ballot_w64(fix) != 0) {           // some lane of the wave holds such a pair
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int row = k4 + 4 * r;
-                        if (d2[r] < 1e-5 * (na4[r] + nb) && row < anr && colSeg[buf][i16] >= 0) {      // (row < N and column < M)
+                        if (d2[r] < GRAM_SWITCH * (na4[r] + nb) && row < anr && colSeg[buf][i16] >= 0) {      // (row < N and column < M)
                             const double* xa = a.X + (size_t)(ar0 + row) * DIM;
                             const double* xb = a.G + (size_t)(br0 + i16) * DIM;
                             double e = 0.0;

@@ -454,6 +454,10 @@ void mirror_upper_dev(Ctx* c, double* dD, int T);
 inline size_t dist_matrix_bytes(int T) { return (size_t)T * T * sizeof(double) + (size_t)T * 64 + 4096; }
 int hac_dev(Ctx* c, double* d_D, const int32_t* row_start, int T, double threshold, int32_t* labels, double* merge_log,
             const double* extent = nullptr, int32_t* n_blocked = nullptr, int flags = 0);
+// The two mean-distance tile kernels (pair_tiles_k, cross_tiles_k) form d^2 = |a|^2 + |b|^2 - 2 a.b on the f64 matrix cores and leave that
+// Gram form for the summed squared differences where d^2 < GRAM_SWITCH (|a|^2 + |b|^2).  DESIGN.md ("K10: where the Gram form ends") has
+// the measurements behind the value.
+constexpr double GRAM_SWITCH = 1e-3;
 // identification against a gallery (identify.hip): the checks of a call (host, before any device work), the T x K block means
 // (left in s_clu1 and returned; also copied to D_host when given), and the decision per group on a device or a host matrix
 void identify_check_dist(const char* who, int N, const int32_t* row_start, int T, int M, const int32_t* gal_start, int K, int dim, int metric);
