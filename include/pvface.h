@@ -576,6 +576,30 @@ int32_t pvf_search(pvf_handle ctx, const double* Qrows, int32_t Q, const double*
                    int32_t* idx /* Q x k */, int64_t* d2 /* Q x k */, int32_t* count /* Q */);
 int32_t pvf_search_plan(int32_t Q, int64_t N, int32_t k, int64_t out[6]);
 
+/* ---- cast: rank-order clustering on an exact k-NN graph (CAST.md) ---------------------------------------------------------------------
+ * WHO the people of many films are: the N rows of X float64 [N][dim] are grouped into persons.  There is NO REFERENCE CALL.  Every rule is
+ * stated in integers (CAST.md), so labels are a pure function of the inputs.
+ *   nodes      rows are quantised and refused as pvf_search does (the message names X[r][c]).  group int32 [N], or NULL: negative = none,
+ *              else a value in 0 .. N-1; rows of equal group start joined and never appear in each other's lists.
+ *   lists      L_a = the hits of pvf_search for row a against the whole table by (d2, row), the first k, under the cut max_d2 (-1: none),
+ *              without a itself and without the rows of a's group.  c_a = len(L_a); O_a(b) = 1-based position of b in L_a.
+ *   links      for b in L_a: miss(x -> y) = #{z in L_x[0:p] : z != y, z not in L_y}, p = O_x(y) or c_x when y is not in L_x;
+ *              m = miss(a -> b) + miss(b -> a); r = the smaller of the ranks O_a(b), O_b(a) that exist; linked when m * den <= num * r.
+ *   labels     connected components of links + group edges; labels[a] = the smallest row of a's component; n_components (may be NULL).
+ * Checked on the host before any device work: dim == 128; 1 <= N <= 2^24; 1 <= k <= 256; max_d2 >= -1; 0 <= num <= 2^20; 1 <= den <= 2^20;
+ * groups negative or below N.  The table is uploaded once and stays on the device; the lists never leave it.  PVF_CAST_QBLOCK (read at
+ * every call; the test switch) sets the query rows per batch, PVF_SEARCH_CHUNK the table rows per chunk.
+ * pvf_debug_cast_lists: the lists -- idx int32 [N][k], d2 int64 [N][k], both -1 past count [N].
+ * pvf_debug_cast_links: per (a, slot) m and r (int32 [N][k], -1 past the count) and linked (uint8 [N][k], 0 past the count).
+ * pvf_cast_plan (host only): out = {query rows per batch, batches, table rows per chunk, chunks, column ranges per chunk, device bytes}. */
+int32_t pvf_cast(pvf_handle ctx, const double* X, int64_t N, int32_t dim, int32_t k, int64_t max_d2, int64_t num, int64_t den,
+                 const int32_t* group /* N, or NULL */, int32_t* labels /* N */, int32_t* n_components /* or NULL */);
+int32_t pvf_debug_cast_lists(pvf_handle ctx, const double* X, int64_t N, int32_t dim, int32_t k, int64_t max_d2, const int32_t* group,
+                             int32_t* idx, int64_t* d2, int32_t* count);
+int32_t pvf_debug_cast_links(pvf_handle ctx, const double* X, int64_t N, int32_t dim, int32_t k, int64_t max_d2, int64_t num, int64_t den,
+                             const int32_t* group, int32_t* m, int32_t* r, uint8_t* linked);
+int32_t pvf_cast_plan(int64_t N, int32_t k, int64_t out[6]);
+
 /* ---- footage shared between films (REPEAT.md; no reference call) -----------------------------------------------------------------
  * A print of a frame is four uint64: H, V, SY | RANGE << 32 and a word for the caller.  With G the 9 x 9 thumbnail of the whole frame
  * (pvf_frame_thumbs' exact area average, tw = th = 9; a side below 9 replicates) and Y[r][c] = (77 R + 150 G + 29 B + 128) >> 8 of it:

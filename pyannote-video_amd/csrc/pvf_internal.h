@@ -466,3 +466,19 @@ double* gallery_mean_dist_dev(Ctx* c, const double* X, int N, const int32_t* row
                               int K, int metric, double* D_host);
 void identify_pick_dev(Ctx* c, const double* d_D, const double* D_host, int T, int K, double threshold, int32_t* best, double* best_dist,
                        int32_t* second, double* second_dist);
+// the exact k nearest rows (search.hip): the arguments of search_tiles_k, how a call is cut, and the kernels as cast.hip runs them on
+// row ranges of a table that stays on the device (on c->stream; no profiling scope of their own)
+struct SrArgs {
+    const float* Qf; const double* nq; const int* qgrp;          // quantised queries [nbq * 16][128] (zero rows past Q), |q|^2, group or -1
+    const float* Xf; const double* nx; const int* rgrp;          // this chunk: quantised rows [n][128], |x|^2, group (nullptr: none)
+    int Q, nbq, n, row0;                                          // row0: table index of the chunk's first row
+    int range_blocks, n_ranges, k, kp;
+    double cut;                                                   // max_d2, negative: no cut
+    long long* a_d2; int* a_idx; int* a_cnt;                      // arena [query row][range][2 kp] (list, then pending); list lengths
+    const unsigned long long* flag;                               // [0] queries, [1] table: position of the first refused value
+};
+struct SrPlan { int64_t chunk_rows, n_chunks, n_ranges, range_blocks, kp, arena_entries; };
+SrPlan search_plan_of(int Q, int64_t N, int k);
+void search_quant_launch(Ctx* c, const double* X, int n, long long row0, float* out, double* nrm, unsigned long long* flag);
+void search_tiles_launch(Ctx* c, const SrArgs& a);
+void search_merge_launch(Ctx* c, const SrArgs& a, int32_t* idx, long long* d2, int32_t* count);

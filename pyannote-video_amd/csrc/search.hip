@@ -33,16 +33,6 @@ static constexpr int SR_DIM = 128, SR_MAX_K = 1024, SR_MIN_BUF = 64, SR_RANGE_MI
 static constexpr int64_t SR_DEFAULT_CHUNK = 1 << 18, SR_ARENA_MAX = (int64_t)1 << 30;
 static constexpr double SR_Q_MAX = 1048576.0;        // 2^20
 
-struct SrArgs {
-    const float* Qf; const double* nq; const int* qgrp;          // quantised queries [nbq * 16][128] (zero rows past Q), |q|^2, group or -1
-    const float* Xf; const double* nx; const int* rgrp;          // this chunk: quantised rows [n][128], |x|^2, group (nullptr: none)
-    int Q, nbq, n, row0;                                          // row0: table index of the chunk's first row
-    int range_blocks, n_ranges, k, kp;
-    double cut;                                                   // max_d2, negative: no cut
-    long long* a_d2; int* a_idx; int* a_cnt;                      // arena [query row][range][2 kp] (list, then pending); list lengths
-    const unsigned long long* flag;                               // [0] queries, [1] table: position of the first refused value
-};
-
 __global__ void __launch_bounds__(256) search_quant_k(const double* __restrict__ X, int n, long long row0, float* __restrict__ out,
                                                       double* __restrict__ nrm, unsigned long long* __restrict__ flag)
 {
@@ -316,7 +306,6 @@ __global__ void __launch_bounds__(256) search_merge_k(const long long* __restric
 }
 
 namespace {
-struct SrPlan { int64_t chunk_rows, n_chunks, n_ranges, range_blocks, kp, arena_entries; };
 
 // every limit of a call, on the host, before any device work
 void search_check(int Q, int64_t N, int dim, int k, int64_t max_d2, const int32_t* query_group, const int32_t* row_group)
@@ -441,6 +430,22 @@ void search_dev(Ctx* c, const double* Qrows, int Q, const double* X, int64_t N, 
     HIP_CHECK(hipStreamSynchronize(c->stream));
 }
 } // namespace
+
+// ---- what cast.hip runs of this file (declared in pvf_internal.h): the plan and the three kernels, on c->stream, unchanged
+SrPlan search_plan_of(int Q, int64_t N, int k) { return search_plan(Q, N, k); }
+void search_quant_launch(Ctx* c, const double* X, int n, long long row0, float* out, double* nrm, unsigned long long* flag)
+{
+    hipLaunchKernelGGL(search_quant_k, dim3((n + 3) / 4), dim3(256), 0, c->stream, X, n, row0, out, nrm, flag);
+}
+void search_tiles_launch(Ctx* c, const SrArgs& a)      // (a.kp <= 256: the dynamic LDS stays below the default limit)
+{
+    hipLaunchKernelGGL(search_tiles_k, dim3((a.nbq + 3) / 4, a.n_ranges), dim3(256), (size_t)4 * 2 * a.kp * 12, c->stream, a);
+}
+void search_merge_launch(Ctx* c, const SrArgs& a, int32_t* idx, long long* d2, int32_t* count)
+{
+    hipLaunchKernelGGL(search_merge_k, dim3(a.Q), dim3(256), (size_t)2 * a.kp * 12, c->stream, a.a_d2, a.a_idx, a.a_cnt, a.n_ranges, a.k, a.kp, a.flag,
+                       idx, d2, count);
+}
 
 #define API_BEGIN try {
 #define API_END                                                        \

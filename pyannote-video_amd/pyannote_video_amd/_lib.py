@@ -143,6 +143,11 @@ _SIGS = {
     "pvf_identify": (C.c_int32, [H, P, C.c_int32, P, C.c_int32, P, C.c_int32, P, C.c_int32, C.c_int32, C.c_int32, C.c_double, P, P, P, P, P]),
     "pvf_search": (C.c_int32, [H, P, C.c_int32, P, C.c_int64, C.c_int32, C.c_int32, C.c_int64, P, P, P, P, P]),
     "pvf_search_plan": (C.c_int32, [C.c_int32, C.c_int64, C.c_int32, P]),
+    # rank-order clustering on the exact k-NN graph (CAST.md)
+    "pvf_cast": (C.c_int32, [H, P, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, P, P, P]),
+    "pvf_debug_cast_lists": (C.c_int32, [H, P, C.c_int64, C.c_int32, C.c_int32, C.c_int64, P, P, P, P]),
+    "pvf_debug_cast_links": (C.c_int32, [H, P, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, P, P, P, P]),
+    "pvf_cast_plan": (C.c_int32, [C.c_int64, C.c_int32, P]),
     # the fingerprint and repeat verbs (REPEAT.md): a frame's 128-bit print, and the runs of matching prints along the diagonals
     "pvf_frame_prints": (C.c_int32, [H, P, C.c_int32, P, C.c_int32]),
     "pvf_print_runs": (C.c_int32, [H, P, P, C.c_int32, P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P, C.c_int64, P]),

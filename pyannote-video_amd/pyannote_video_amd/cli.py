@@ -14,6 +14,8 @@
     python -m pyannote_video_amd identify [--threshold 0.6] [--metric euclidean|cosine] [--labels PATH] [--unknown NAME] [--scores PATH] <embeddings> <gallery> <output>
     python -m pyannote_video_amd search  [-k 100] [--max-distance D] [--rows] [--include-self] (--gallery PATH --name NAME | --from EMBEDDINGS --track ID)
                                          <output> <embeddings> [<embeddings> ...]
+    python -m pyannote_video_amd cast    [-k 64] [--max-distance 0.6] [--threshold 2.0] [--by track|face] [--labels SUFFIX] [--graph PATH]
+                                         <output> <embeddings> [<embeddings> ...]
     python -m pyannote_video_amd demo    [--height 400] [--from 0] [--until T] [--shift 0] [--landmark PATH] [--label PATH] <video> <tracking> <output>
     python -m pyannote_video_amd redact  [--height 0] [--from 0] [--until T] [--shift 0] [--label PATH] [--only A,B | --keep A,B] [--pad 25] [--cells 8]
                                          [--shape ellipse|box] [--mode mosaic|smooth|fill] [--colour r,g,b] [--draw] <video> <tracking> <output>
@@ -33,6 +35,8 @@ only (face/clustering.py:130-134).  It writes `identifier label` lines, the file
 `identify` writes `identifier name` lines, the same file `demo --label` reads; `process --gallery` does it in the same run.
 `search` (search.py; no reference verb; SEARCH.md) answers "where else does this face appear?": the exact k nearest faces of one or more
 embedding files to a track or to a person of a gallery, one `rank distance path track T` line per hit, nearest first.
+`cast` (cast.py; no reference verb; CAST.md) answers "who are the people of these films?": rank-order clustering on the exact k-NN graph of
+the tracks (or faces) of any number of embedding files, one `path track person` line per (file, track).
 `demo` (pyannote-face.py:317-413) writes the video with the tracks, their numbers and labels and, with --landmark, the nose lines drawn
 on it, as a YUV4MPEG2 stream: to a `.y4m` path, or to stdout for `-` (`... demo film.y4m track.txt - | ffmpeg -i - out.mp4`).  Resize,
 drawing and RGB -> YUV 4:2:0 run in one kernel on the GPU (DEMO.md states every pixel; the font is the project's own, not OpenCV's
@@ -381,6 +385,21 @@ def search(output, embeddings, k=100, max_distance=None, rows=False, include_sel
     hits = fs.search(query, k=k, max_distance=max_distance, exclude_group=own, collapse=not rows)
     _search.write_hits(output, hits)
     return hits
+
+
+def cast(output, embeddings, k=64, max_distance=0.6, threshold=2.0, by="track", labels=None, graph=None, ctx=None):
+    """The persons of one or more embedding files: `path track person` lines, one per (file, track), in the order of the files and then
+    by track (`output`: a path, or - for stdout); persons are numbered 0, 1, ... .  labels: a suffix -- `<embeddings><suffix>` gets the
+    file's `identifier label` lines for `demo --label`; graph: a path that gets the k-NN lists as an .npz.  -> the lines"""
+    from . import cast as _cast
+    fc = _cast.FaceCast(ctx=ctx)
+    for path in embeddings:
+        fc.add(path)
+    lines = fc.run(k=k, max_distance=max_distance, threshold=threshold, by=by, graph=graph)
+    _cast.write_cast(output, lines)
+    if labels is not None:
+        _cast.write_label_files(lines, labels)
+    return lines
 
 
 def enroll_track(embeddings, track, name, gallery, append=False):
@@ -1007,6 +1026,15 @@ def _parser():
     en.add_argument("--jitters", type=int, default=0, help="descriptors averaged over this many jittered face chips (dlib's num_jitters; "
                     "0 or 1: the plain descriptor)")
     en.add_argument("--jitter-seed", type=int, default=0, help="seed of the jitter transforms (they depend on the seed and the jitter's index alone)")
+    ca = sub.add_parser("cast", help="the persons of one or more embedding files: rank-order clustering on the exact k-NN graph")
+    ca.add_argument("output", help="a path, or - for stdout: `path track person` lines")
+    ca.add_argument("embeddings", nargs="+", help="the embedding files whose tracks are grouped into persons")
+    ca.add_argument("-k", type=int, default=64, help="neighbours per node (1 .. 256)")
+    ca.add_argument("--max-distance", type=float, default=0.6, help="no neighbour further than this")
+    ca.add_argument("--threshold", type=float, default=2.0, help="a pair is linked when its missing neighbours are at most this many per rank")
+    ca.add_argument("--by", default="track", help="track: one node per (file, track), its mean descriptor; face: one node per row")
+    ca.add_argument("--labels", default=None, metavar="SUFFIX", help="also write <embeddings>SUFFIX beside each file: `identifier label` lines")
+    ca.add_argument("--graph", default=None, metavar="PATH", help="also write the k-NN lists and the node table as an .npz")
     se = sub.add_parser("search", help="the exact k nearest faces of one or more embedding files to a track or to a person of a gallery")
     se.add_argument("output", help="a path, or - for stdout: `rank distance path track T` lines, nearest first")
     se.add_argument("embeddings", nargs="+", help="the embedding files that are searched")
@@ -1147,6 +1175,11 @@ def main(argv=None):
                      jitter_seed=a.jitter_seed)
     elif a.verb == "enroll-track":
         enroll_track(a.embeddings, a.track, a.name, a.gallery, append=a.append)
+    elif a.verb == "cast":
+        try:
+            cast(a.output, a.embeddings, k=a.k, max_distance=a.max_distance, threshold=a.threshold, by=a.by, labels=a.labels, graph=a.graph, ctx=ctx)
+        except ValueError as e:
+            ap.error(str(e))
     elif a.verb == "search":
         try:
             search(a.output, a.embeddings, k=a.k, max_distance=a.max_distance, rows=a.rows, include_self=a.include_self, gallery=a.gallery,

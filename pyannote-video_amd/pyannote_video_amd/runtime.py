@@ -1116,6 +1116,49 @@ class Context(object):
         check(_lib.lib().pvf_search_plan(int(Q), int(N), int(k), ptr(out)))
         return dict(zip(("chunk_rows", "n_chunks", "n_ranges", "range_blocks", "pending", "arena_bytes"), (int(v) for v in out)))
 
+    # ---- cast: rank-order clustering on the exact k-NN graph (pvf_cast; CAST.md states the rules in integers)
+    @staticmethod
+    def _cast_table(X, group):
+        X = np.ascontiguousarray(X, np.float64)
+        if X.ndim != 2:
+            raise ValueError("cast: X [N, dim] is expected")
+        g = None
+        if group is not None:
+            g = np.ascontiguousarray(group, np.int32)
+            if g.shape != (X.shape[0],):
+                raise ValueError("cast: one group per row")
+        return X, g
+
+    def cast(self, X, k, max_d2=-1, num=2000, den=1000, group=None):
+        """-> (labels int32 [N], n_components): the smallest row of every row's component under the links of CAST.md"""
+        X, g = self._cast_table(X, group)
+        labels, n = np.full(X.shape[0], -1, np.int32), C.c_int32(0)
+        check(self._l.pvf_cast(self._h, ptr(X), X.shape[0], X.shape[1], int(k), int(max_d2), int(num), int(den), ptr(g), ptr(labels), C.byref(n)))
+        return labels, n.value
+
+    def cast_lists(self, X, k, max_d2=-1, group=None):
+        """-> (idx int32 [N, k], d2 int64 [N, k], count int32 [N]): the list of every row, -1 past count"""
+        X, g = self._cast_table(X, group)
+        N, kk = X.shape[0], min(max(int(k), 0), 256)
+        idx, d2, count = np.full((N, kk), -1, np.int32), np.full((N, kk), -1, np.int64), np.zeros(N, np.int32)
+        check(self._l.pvf_debug_cast_lists(self._h, ptr(X), N, X.shape[1], int(k), int(max_d2), ptr(g), ptr(idx), ptr(d2), ptr(count)))
+        return idx, d2, count
+
+    def cast_links(self, X, k, max_d2=-1, num=2000, den=1000, group=None):
+        """-> (m int32 [N, k], r int32 [N, k], linked uint8 [N, k]) per (row, slot of its list); -1, -1, 0 past the list"""
+        X, g = self._cast_table(X, group)
+        N, kk = X.shape[0], min(max(int(k), 0), 256)
+        m, r, linked = np.full((N, kk), -1, np.int32), np.full((N, kk), -1, np.int32), np.zeros((N, kk), np.uint8)
+        check(self._l.pvf_debug_cast_links(self._h, ptr(X), N, X.shape[1], int(k), int(max_d2), int(num), int(den), ptr(g), ptr(m), ptr(r), ptr(linked)))
+        return m, r, linked
+
+    @staticmethod
+    def cast_plan(N, k):
+        """how pvf_cast cuts a call of these sizes -> dict(qblock, n_batches, chunk_rows, n_chunks, n_ranges, device_bytes)"""
+        out = np.zeros(6, np.int64)
+        check(_lib.lib().pvf_cast_plan(int(N), int(k), ptr(out)))
+        return dict(zip(("qblock", "n_batches", "chunk_rows", "n_chunks", "n_ranges", "device_bytes"), (int(v) for v in out)))
+
     # ---- the fingerprint and repeat verbs (REPEAT.md)
     def frame_prints(self, frames, out_ptr=None):
         """resident frames, of any sizes, as prints (pvf_frame_prints): uint64 [n, 4] = H, V, SY | RANGE << 32, 0.  With out_ptr, a
