@@ -624,6 +624,29 @@ int32_t pvf_print_runs(pvf_handle ctx, const uint64_t* A /* NA*2: H, V */, const
                        int32_t tau, int32_t min_len, int32_t min_gap,
                        int32_t* runs /* cap*3 */, int64_t cap, int64_t* found);
 
+/* ---- fades and dissolves (BLEND.md; no reference call) ---------------------------------------------------------------------------
+ * The blend record of a frame is a row of 16 uint32.  With G the tw x th thumbnail of the whole frame (the exact area average of the
+ * storyboard's thumbnails), Y = (77 R + 150 G + 29 B + 128) >> 8 of it, P = tw th pixels: word 0 is P, words 1 .. 3 are S1 = sum Y,
+ * S2 = sum Y^2 and E1 = sum |Y_t - Y_(t-1)|; words 4 .. 11 are E_L = sum |Y_t - Y_(t-L)| and R_L = sum |2 Y_(t-L/2) - Y_(t-L) - Y_t| for
+ * L = 4, 8, 16, 32; words 12 and 13 are the caller's (written as 0), word 14 is tw | th << 16, word 15 is 0.  A sum whose earlier frame
+ * does not exist is 0xFFFFFFFF.
+ * The first call below measures n resident frames of one size.  hist holds the luma planes of the nh <= PVF_BLEND_MAX_HISTORY frames in
+ * front of frames[0], oldest first; luma_out, when given, receives the planes of the n frames, of which the caller carries the last 32
+ * into its next call.  The call keeps no state.  The second call measures rows first .. N - 1 of planes the caller made itself, with the
+ * rows in front of them as history; S1 and S2 come from the planes and word 14 is 0.  n = 0, or first = N, does nothing.
+ * Refused before any work: n, N or first negative, n beyond PVF_THUMB_MAX_FRAMES, N beyond PVF_BLEND_MAX_ROWS, first > N, nh outside
+ * 0 .. 32, tw or th outside 1 .. PVF_THUMB_MAX_SIDE, P outside 1 .. PVF_BLEND_MAX_PIXELS, null pointers where a count is positive, an
+ * unknown or released frame, frames of different sizes. */
+#define PVF_BLEND_MAX_PIXELS 16384       /* tw * th: every sum of a row fits 32 bits */
+#define PVF_BLEND_MAX_HISTORY 32         /* the largest lag */
+#define PVF_BLEND_ROW_WORDS 16
+#define PVF_BLEND_MAX_ROWS 16777216      /* planes of one call on planes */
+int32_t pvf_frame_blend(pvf_handle ctx, const pvf_handle* frames, int32_t n, int32_t tw, int32_t th,
+                        const uint8_t* hist /* nh*P, host */, int32_t nh, uint32_t* rows /* n*16, host */,
+                        uint8_t* luma_out /* n*P host, or NULL */);
+int32_t pvf_blend_measure(pvf_handle ctx, const uint8_t* luma /* N*P, host */, int32_t N, int32_t P, int32_t first,
+                          uint32_t* rows /* (N-first)*16 */);
+
 /* ---- file formats (host) ------------------------------------------------------------------------------ */
 /* ref: scripts/pyannote-face.py:299-311  the lines of landmarks.txt / embedding.txt: "{t:.3f} {identifier:d}" + n_cols x " {v:.<decimals>f}"
  * + newline per row, byte for byte what Python's format writes (both are the correctly rounded decimal).  values [n_rows][n_cols];

@@ -292,6 +292,10 @@ static void thumbs_run(Ctx* c, const pvf_handle* frames, int n, int tw, int th, 
     HIP_CHECK(hipStreamSynchronize(c->stream));
 }
 
+// for blend.hip: the thumbnails of resident frames of one size into device memory, and the frames of a round at a picture size
+void board_thumbs_device(Ctx* c, const pvf_handle* frames, int n, int tw, int th, uint8_t* d_out) { thumbs_run(c, frames, n, tw, th, 0, d_out, true); }
+int board_thumbs_per_round(size_t picture_bytes) { return thumbs_per_round(picture_bytes); }
+
 static void thumb_sheet_run(Ctx* c, const uint8_t* thumbs, int n, const int32_t* xy, int tw, int th, int W, int H, uint32_t background,
                             const pvf_prim* prims, int n_prims, const uint8_t* text, int64_t text_bytes, uint8_t* rgb)
 {

@@ -370,6 +370,8 @@ ResizeTab linear_table(int in, int out);
 void render_free_all(Ctx* c);            // render.hip: resize tables, scratch and egress rings of the context
 void tube_free_all(Ctx* c);              // tube.hip: output buffers, copy stream and events of pvf_frame_crops
 void board_free_all(Ctx* c);             // board.hip: the same of pvf_frame_thumbs
+void board_thumbs_device(Ctx* c, const pvf_handle* frames, int n, int tw, int th, uint8_t* d_out);    // board.hip: frame_thumbs_k for blend.hip
+int board_thumbs_per_round(size_t picture_bytes);      // board.hip: pictures of a round (PVF_THUMB_ROUND)
 void det_nms(const DetectorModel& m, const std::vector<RawDet>& sorted, std::vector<RawDet>& out);
 void det_pyramid_level(Ctx* c, const Frame& f, int upsample, int level, std::vector<uint8_t>* out, int* h, int* w);
 void det_level_features(Ctx* c, const Frame& f, int upsample, int level, std::vector<float>* out, int* fh, int* fw);

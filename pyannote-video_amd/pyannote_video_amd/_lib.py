@@ -151,6 +151,9 @@ _SIGS = {
     # the fingerprint and repeat verbs (REPEAT.md): a frame's 128-bit print, and the runs of matching prints along the diagonals
     "pvf_frame_prints": (C.c_int32, [H, P, C.c_int32, P, C.c_int32]),
     "pvf_print_runs": (C.c_int32, [H, P, P, C.c_int32, P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P, C.c_int64, P]),
+    # the blend and transition verbs (BLEND.md): a frame's blend record, from resident frames or from luma planes of the caller's
+    "pvf_frame_blend": (C.c_int32, [H, P, C.c_int32, C.c_int32, C.c_int32, P, C.c_int32, P, P]),
+    "pvf_blend_measure": (C.c_int32, [H, P, C.c_int32, C.c_int32, C.c_int32, P]),
     "pvf_format_rows": (C.c_int32, [P, P, P, C.c_int64, C.c_int32, C.c_int32, P, C.c_int64, P]),
     "pvf_round_rows": (C.c_int32, [P, C.c_int64, C.c_int32, P]),
     "pvf_parse_rows": (C.c_int32, [C.c_char_p, C.c_int64, P, C.c_int64, P, P]),

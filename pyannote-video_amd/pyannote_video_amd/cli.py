@@ -27,6 +27,9 @@
     python -m pyannote_video_amd fingerprint [--from 0] [--until T] [--batch 64] <video> <prints.npy>
     python -m pyannote_video_amd repeat  [--max-bits 10] [--flat 16] [--min-duration 2.0] [--max-gap 0.5] [--min-separation 5.0]
                                          <output.json> <prints.npy> [<prints.npy> ...]
+    python -m pyannote_video_amd blend   [--width 64] [--from 0] [--until T] [--batch 64] <video> <blend.npy>
+    python -m pyannote_video_amd transition [--move 4.0] [--linear 0.25] [--flat 2.0] [--min-duration 0.12] [--shots IN --refined OUT]
+                                         <blend.npy> <output.json>
 
 `track` and `extract` take the reference's arguments and options and write byte-compatible files (track.txt, landmarks.txt,
 embedding.txt: formats.py).  `cluster` is the verb BASELINE.json's north_star names; the reference offers clustering through the API
@@ -58,12 +61,16 @@ thumbnails under the shot's number and start, coloured and with --by thread line
 `fingerprint` (no reference verb; REPEAT.md) writes a 128-bit print of every frame, made on the GPU from the frame's 9 x 9 thumbnail, as a
 uint64 [n][4] `.npy`; `repeat` compares print files with themselves and with each other and writes the stretches they share -- a recap,
 the titles, a rerun -- as JSON.  The thresholds are untuned; the runs and segments are the product.
+`blend` (no reference verb; BLEND.md) writes the blend record of every frame -- how far the luma of a small thumbnail lies from the frames
+4, 8, 16 and 32 before it, and how far the frame in the middle lies off the line between the two, summed on the GPU -- as a uint32 [n][16]
+`.npy`; `transition` reads that file alone and writes the fades, dissolves and blank stretches it shows as JSON and, with --shots and
+--refined, the shots of `shot` cut at them, which `track`, `thread` and `storyboard` read unchanged.  The thresholds are untuned.
 
 <video>: no codec is linked (reference video.py:345-406 runs ffmpeg); the verbs read what a decoder writes --
   * a YUV4MPEG2 file (`.y4m`, or any file that starts with `YUV4MPEG2`): 8-bit 4:2:0 / 4:2:2 / 4:4:4, memory mapped, frame rate from
     its header (`ffmpeg -i film.mkv -pix_fmt yuv420p -f yuv4mpegpipe film.y4m`); the planes go to the GPU as they are and are
     converted to RGB there (--matrix 601|709, --range limited|full override the header);
-  * `-`: the same stream from stdin, for the verbs that read the video once and need no length (`track`, `process`, `talk`, `fingerprint`):
+  * `-`: the same stream from stdin, for the verbs that read the video once and need no length (`track`, `process`, `talk`, `fingerprint`, `blend`):
     `ffmpeg -i film.mkv -pix_fmt yuv420p -f yuv4mpegpipe - | python -m pyannote_video_amd process - ...`;
   * a `.npy` file holding uint8 [N, H, W, 3] RGB frames (memory mapped; frame rate from --fps);
   * the bench's synthetic clip: `synthetic:<width>x<height>x<frames>[:shots[:faces[:seed]]]`.
@@ -590,6 +597,80 @@ def repeat(output, prints, max_bits=10, flat=16, min_duration=2.0, max_gap=0.5, 
     return found
 
 
+def blend(video, output, width=64, t_from=0.0, t_until=None, batch=64, ctx=None, ahead=96):
+    """The blend record of every frame of the video whose time lies in [t_from, t_until) (BLEND.md): one streaming pass as `fingerprint`
+    makes it; `batch` resident frames per frame_blend call, the last 32 luma planes carried into the next call (blend.Carry), so the
+    file does not depend on `batch`.  The thumbnail is `width` pixels wide and keeps the frame's aspect.  Writes uint32 [n][16], stamped
+    with ms(T) and the frame index, as a .npy file (`output` may be an open binary file).  Returns {"frames", "first", "tw", "th"}."""
+    from . import blend as _blend, repeat as _repeat, runtime
+    from .feed import FrameFeed
+    if int(batch) < 1:
+        raise ValueError("blend: a batch holds at least one frame")
+    if int(width) < 1:
+        raise ValueError("blend: --width is at least 1")
+    rate = float(video.frame_rate)
+    w, h = video.frame_size
+    tw, th = _blend.tile_size(width, w, h)
+    first = 0
+    while first / rate < t_from:
+        first += 1
+    end = None
+    if t_until is not None:
+        end = first
+        while end / rate < t_until:
+            end += 1
+    try:
+        end = len(video) if end is None else min(end, len(video))
+    except TypeError:                        # a stream: as far as it goes
+        pass
+    ctx = ctx or runtime.default_context()
+    carry = _blend.Carry(ctx, tw, th)
+    parts, pend = [], []
+    with FrameFeed(ctx, video, _repeat.EveryFrame(first, end), ahead=max(ahead, 2 * int(batch)), name="pvface-blend-reader") as feed:
+        def flush():
+            parts.append(carry.measure(pend))
+            feed.release_all(pend)
+            del pend[:]
+        for _, dev in feed:
+            pend.append(dev)
+            if len(pend) >= batch:
+                flush()
+        if pend:
+            flush()
+    rows = _blend.stamp(np.concatenate(parts) if parts else np.zeros((0, _blend.WORDS), np.uint32), first, rate)
+    if hasattr(output, "write"):
+        np.save(output, rows)
+    else:
+        with open(output, "wb") as fo:
+            np.save(fo, rows)
+    return {"frames": int(len(rows)), "first": first, "tw": tw, "th": th}
+
+
+def transition(rows, output, move=4.0, linear=0.25, flat=2.0, min_duration=0.12, shots=None, refined=None):
+    """Fades, dissolves and blank stretches from a blend file (BLEND.md), on the host: a JSON list of {kind, start, end, first, last}.
+    With `shots` (what `shot` wrote) and `refined`, also the Timeline of `shot` cut at the middle of every dissolve and of every blank
+    run a fade ends in or starts from.  The video is not opened.  Returns the list."""
+    from . import blend as _blend
+    if (shots is None) != (refined is None):
+        raise ValueError("transition: --shots and --refined go together")
+    table = _blend.load(rows) if isinstance(rows, str) else np.ascontiguousarray(rows)
+    found, cuts = _blend.analyse(table, move=move, linear=linear, flat=flat, min_duration=min_duration)
+    listed = _blend.report(table, found)
+    text = json.dumps(listed, indent=1)
+    if str(output) == "-":
+        sys.stdout.write(text + "\n")
+        sys.stdout.flush()
+    else:
+        with open(output, "w") as fo:
+            fo.write(text + "\n")
+    if shots is not None:
+        before = [(s.start, s.end) for s in (load_shots(shots) if isinstance(shots, str) else shots)]
+        pieces = _blend.refine(before, [int(table[c, 12]) / 1000.0 for c in cuts])
+        with open(refined, "w") as fp:
+            json.dump({"pyannote": "Timeline", "content": [{"start": a, "end": b} for a, b in pieces]}, fp)
+    return listed
+
+
 def demo(video, tracking, output, height=400, t_from=0.0, t_until=None, shift=0.0, landmark=None, label=None, matrix="601",
          full_range=False, fps=None, ctx=None, ring_depth=16):
     """Annotated video (pyannote-face.py:317-413) as YUV4MPEG2, to a path or to stdout (`-`).  What is drawn on which frame is planned
@@ -1005,6 +1086,20 @@ def _parser():
     rp.add_argument("--min-duration", type=float, default=2.0, help="segments shorter than this are dropped, seconds")
     rp.add_argument("--max-gap", type=float, default=0.5, help="runs of one offset this close are one segment, seconds")
     rp.add_argument("--min-separation", type=float, default=5.0, help="within one file: only footage at least this far apart, seconds")
+    bl = sub.add_parser("blend", help="the blend record of every frame of a video, as a uint32 [n][16] .npy file")
+    bl.add_argument("video"); bl.add_argument("output", help="the .npy path the rows are written to")
+    bl.add_argument("--width", type=int, default=64, help="width of the thumbnail that is measured; the height keeps the frame's aspect")
+    bl.add_argument("--from", dest="t_from", type=float, default=0.0, help="frames at or after this, seconds")
+    bl.add_argument("--until", dest="t_until", type=float, default=None, help="frames before this, seconds")
+    bl.add_argument("--batch", type=int, default=64, help="frames measured per library call, and resident at a time")
+    tr = sub.add_parser("transition", help="fades, dissolves and blank stretches from a blend file of `blend`, as JSON; the video is not opened")
+    tr.add_argument("rows", help="the blend file"); tr.add_argument("output", help="a path, or - for stdout")
+    tr.add_argument("--move", type=float, default=4.0, help="least mean change of luma over a window for it to count")
+    tr.add_argument("--linear", type=float, default=0.25, help="largest share of that change the middle frame may lie off the line")
+    tr.add_argument("--flat", type=float, default=2.0, help="a frame whose luma deviates less than this is blank")
+    tr.add_argument("--min-duration", type=float, default=0.12, help="shorter spans and blank runs are dropped, seconds")
+    tr.add_argument("--shots", default=None, help="what `shot` wrote: with --refined, the shots cut at the transitions")
+    tr.add_argument("--refined", default=None, help="where the refined Timeline is written")
     c = sub.add_parser("cluster")
     c.add_argument("embeddings"); c.add_argument("labels")
     c.add_argument("--threshold", type=float, default=0.6)
@@ -1145,7 +1240,7 @@ def main(argv=None):
         if a.video == "-" and a.verb == "faces":
             ap.error("faces reads the video twice, once for the quality of every face and once for the frames of the chosen ones: "
                      "give it a file, not a stream on stdin")
-        if a.video == "-" and a.verb not in ("track", "process", "talk", "tube", "fingerprint"):
+        if a.video == "-" and a.verb not in ("track", "process", "talk", "tube", "fingerprint", "blend"):
             ap.error("%s needs the length of the video: give it a file, not a stream on stdin" % a.verb)
         over = {}
         if a.matrix is not None:
@@ -1210,6 +1305,18 @@ def main(argv=None):
         try:
             repeat(a.output, a.prints, max_bits=a.max_bits, flat=a.flat, min_duration=a.min_duration, max_gap=a.max_gap,
                    min_separation=a.min_separation, ctx=ctx)
+        except ValueError as e:
+            ap.error(str(e))
+    elif a.verb == "blend":
+        if a.batch < 1 or a.width < 1:
+            ap.error("--batch and --width are at least 1")
+        try:
+            res = blend(video(), a.output, width=a.width, t_from=a.t_from, t_until=a.t_until, batch=a.batch, ctx=ctx)
+        except ValueError as e:
+            ap.error(str(e))
+    elif a.verb == "transition":
+        try:
+            transition(a.rows, a.output, move=a.move, linear=a.linear, flat=a.flat, min_duration=a.min_duration, shots=a.shots, refined=a.refined)
         except ValueError as e:
             ap.error(str(e))
     elif a.verb == "demo":

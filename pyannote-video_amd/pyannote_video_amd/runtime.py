@@ -1197,6 +1197,34 @@ class Context(object):
                 return runs[:found.value]
             cap = found.value
 
+    # ---- the blend and transition verbs (BLEND.md)
+    def frame_blend(self, frames, tw, th, hist=None, want_luma=True):
+        """resident frames of one size as blend records (pvf_frame_blend): (rows uint32 [n, 16], luma uint8 [n, tw * th] or None).
+        hist: the luma planes of the up to 32 frames in front of frames[0], oldest first, uint8 [nh, tw * th] -- what an earlier call
+        returned as luma; the call keeps nothing."""
+        n, tw, th = len(frames), int(tw), int(th)
+        P = tw * th if tw > 0 and th > 0 else 0
+        hist = np.zeros((0, P), np.uint8) if hist is None else np.ascontiguousarray(hist, np.uint8)
+        if hist.ndim != 2 or hist.shape[1] != P:
+            raise ValueError("frame_blend: the history is uint8 [nh, tw * th]")
+        rows = np.zeros((n, 16), np.uint32)
+        luma = np.zeros((n, P), np.uint8) if want_luma else None
+        with self._staging():
+            check(self._l.pvf_frame_blend(self._h, ptr(self._handles(frames)), n, tw, th, ptr(hist) if len(hist) else None, len(hist), ptr(rows),
+                                          ptr(luma) if want_luma else None))
+        return rows, luma
+
+    def blend_measure(self, luma, first=0):
+        """-> uint32 [N - first, 16]: the blend records of rows first .. N - 1 of the caller's own luma planes uint8 [N, P], the rows in
+        front of them as history (pvf_blend_measure); S1 and S2 come from the planes, the size word is 0"""
+        luma = np.ascontiguousarray(luma, np.uint8)
+        if luma.ndim != 2:
+            raise ValueError("blend_measure: the planes are uint8 [N, P]")
+        N, P = luma.shape
+        rows = np.zeros((max(N - int(first), 0), 16), np.uint32)
+        check(self._l.pvf_blend_measure(self._h, ptr(luma) if luma.size else None, N, P, int(first), ptr(rows) if rows.size else None))
+        return rows
+
     # The four agglomerating calls have a `_cooccur` sibling that takes `extent` (float64 [T, 2]: start and end of every track, seconds):
     # the do-not-cooccur constraint (clustering.py:142-143; pvf_cluster_*_cooccur) -- tracks whose extents intersect never share a
     # cluster.  They return (labels, merge log, n_blocked = the co-occurring pairs); `flags` bit 0 is the library's test switch
