@@ -647,6 +647,31 @@ int32_t pvf_frame_blend(pvf_handle ctx, const pvf_handle* frames, int32_t n, int
 int32_t pvf_blend_measure(pvf_handle ctx, const uint8_t* luma /* N*P, host */, int32_t N, int32_t P, int32_t first,
                           uint32_t* rows /* (N-first)*16 */);
 
+/* ---- camera motion from the shot detector's flow (MOTION.md; no reference call) ---------------------------------------------------
+ * The motion row of a pair of frames is 10 int64.  The pair's flow, float32 [h][w][2] (component 0 horizontal, 1 vertical, small-image
+ * pixels), is quantised to u, v in 1/64 pixel; a similarity u^ = TX + A X - B Y, v^ = TY + B X + A Y over the centred half-pixel
+ * coordinates X = 2 x - (w - 1), Y = 2 y - (h - 1) is fitted by least squares in integers, then PVF_MOTION_ROUNDS - 1 more times over the
+ * pixels whose residual lies within tau = max(PVF_MOTION_TAU_MIN, twice the mean residual) of the fit before.  Word 0 is
+ * n_valid | n_in << 32; words 1 .. 4 are TX, TY, A, B scaled by 2^16; word 5 the mean residual m; word 6 the sum of |u| + |v| over the valid
+ * pixels; word 7 the bits of the pair's displaced frame difference (0 from pvf_flow_motion); word 8 is the caller's (written as 0);
+ * word 9 is w | h << 16.  MOTION.md states every step.
+ * pvf_flow_motion fits n_pairs flows of the caller's (host).  pvf_shot_motion makes the small gray images and the flows of n resident
+ * frames exactly as pvf_shot_dfd does (`tables` as there), fits the n - 1 flows where they lie on the device and returns the n - 1 rows,
+ * and the n - 1 differences when dfd is not NULL; the flows do not leave the device.  n_pairs = 0 and n <= 1 do nothing.
+ * Refused before any work: a negative count, a side outside PVF_MOTION_MIN_SIDE .. PVF_MOTION_MAX_SIDE, more than PVF_MOTION_MAX_PIXELS
+ * pixels, null pointers where a count is positive, an unknown or released frame, frames of different sizes. */
+#define PVF_MOTION_ROW_WORDS 10
+#define PVF_MOTION_ROUNDS 4
+#define PVF_MOTION_TAU_MIN (16 << 16)    /* 1/4 pixel, in the residual's unit of 2^-22 pixel */
+#define PVF_MOTION_MIN_SIDE 12
+#define PVF_MOTION_MAX_SIDE 256
+#define PVF_MOTION_MAX_PIXELS 16384      /* w * h: every sum of the fit fits 64 bits */
+#define PVF_MOTION_ROUND_PAIRS 256       /* pairs of pvf_flow_motion on the device at a time */
+int32_t pvf_flow_motion(pvf_handle ctx, const float* flow /* n_pairs*h*w*2, host */, int32_t n_pairs, int32_t h, int32_t w,
+                        int64_t* rows /* n_pairs*10, host */);
+int32_t pvf_shot_motion(pvf_handle ctx, const pvf_handle* frames, int32_t n, int32_t width, int32_t height, const float* tables,
+                        int64_t* rows /* (n-1)*10, host */, double* dfd /* n-1 host, or NULL */);
+
 /* ---- file formats (host) ------------------------------------------------------------------------------ */
 /* ref: scripts/pyannote-face.py:299-311  the lines of landmarks.txt / embedding.txt: "{t:.3f} {identifier:d}" + n_cols x " {v:.<decimals>f}"
  * + newline per row, byte for byte what Python's format writes (both are the correctly rounded decimal).  values [n_rows][n_cols];

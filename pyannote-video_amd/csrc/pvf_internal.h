@@ -432,6 +432,11 @@ void dsst_clone_many(Ctx* c, const std::vector<Tracker*>& src, const std::vector
 double* tracker_state_alloc(Ctx* c);
 // shot boundary detection (shot.hip)
 void shot_dfd(Ctx* c, const std::vector<Frame>& frames, int ow, int oh, const float* tables22, double* dfd, uint8_t* gray_out, float* flow_out);
+// the same, and with motion_rows (host, [n - 1][10]) the motion rows of the flows, fitted where shot_pair_k wrote them (motion.hip)
+void shot_run(Ctx* c, const std::vector<Frame>& frames, int ow, int oh, const float* tables22, double* dfd, uint8_t* gray_out, float* flow_out,
+              int64_t* motion_rows);
+// camera motion (motion.hip): motion_fit_k on flows that lie on the device, on c->stream
+void motion_fit_device(Ctx* c, const float* d_flow, int n_pairs, int h, int w, const double* d_dfd, int64_t* d_rows);
 // orb.hip: ORB of the shot threading and its Hamming ratio-test matcher
 std::vector<int> orb_level_quota();
 void orb_extract(Ctx* c, const std::vector<Frame>& frames, int ow, int oh, int cap, int32_t* counts, float* kp_out, uint8_t* desc_out);

@@ -323,6 +323,15 @@ void cv_coeffs(int in, int out, std::vector<Coef>& c)
 // dfd[i] = displaced frame difference between frames i and i + 1 (n - 1 values); optional gray images [n][oh][ow] and flows [n-1][oh][ow][2]
 void shot_dfd(Ctx* c, const std::vector<Frame>& frames, int ow, int oh, const float* tables22, double* dfd, uint8_t* gray_out, float* flow_out)
 {
+    shot_run(c, frames, ow, oh, tables22, dfd, gray_out, flow_out, nullptr);
+}
+
+// shot_dfd, and with motion_rows also pvf_shot_motion: the flows stay in the buffer shot_pair_k writes for flow_out, motion_fit_k (motion.hip)
+// reads them there on the same stream, and [n - 1][10] rows come back; dfd may then be null.  Without motion_rows the layout, the launches
+// and the copies are what they were.
+void shot_run(Ctx* c, const std::vector<Frame>& frames, int ow, int oh, const float* tables22, double* dfd, uint8_t* gray_out, float* flow_out,
+              int64_t* motion_rows)
+{
     const int n = (int)frames.size();
     PVF_REQUIRE(n >= 1 && ow >= 12 && oh >= 12, "shot: at least one frame and a small image of 12 x 12 or more");
     const int ih = frames[0].h, iw = frames[0].w;
@@ -332,16 +341,17 @@ void shot_dfd(Ctx* c, const std::vector<Frame>& frames, int ow, int oh, const fl
     cv_coeffs(ih, oh, cy);
     cv_coeffs(iw, ow, cx);
     const size_t stride = (size_t)px * (1 + 1 + 2 + 3 + 10 + 5 + 5 + 4);
-    const size_t flow_bytes = flow_out ? (size_t)(n - 1) * px * 2 * sizeof(float) : 0;
+    const size_t flow_bytes = flow_out || motion_rows ? (size_t)(n - 1) * px * 2 * sizeof(float) : 0;
     ScratchLayout lay;
     const auto sCoef = lay.take<Coef>(oh + ow); const auto sPtr = lay.take<const uint8_t*>(n);
     const auto sGray = lay.take<uint8_t>((size_t)n * px); const auto sDfd = lay.take<double>(n);
     const auto sFlow = lay.take<float>(flow_bytes / sizeof(float)), sScratch = lay.take<float>((size_t)std::max(n - 1, 1) * stride);
+    const auto sMotion = lay.take<int64_t>(motion_rows ? (size_t)(n - 1) * PVF_MOTION_ROW_WORDS : 0);    // (nothing without motion_rows)
     lay.pad(256);                                             // reason unknown, kept
     c->s_misc.ensure(lay.bytes());
     Coef* d_coef = sCoef.in(c->s_misc); const uint8_t** d_ptr = sPtr.in(c->s_misc);
     uint8_t* d_gray = sGray.in(c->s_misc); double* d_dfd = sDfd.in(c->s_misc);
-    float* d_flow = flow_out ? sFlow.in(c->s_misc) : nullptr;
+    float* d_flow = flow_bytes ? sFlow.in(c->s_misc) : nullptr;
     float* d_scratch = sScratch.in(c->s_misc);
     std::vector<Coef> both(cy);
     both.insert(both.end(), cx.begin(), cx.end());
@@ -359,7 +369,12 @@ void shot_dfd(Ctx* c, const std::vector<Frame>& frames, int ow, int oh, const fl
         const FbPlan plan = farneback_plan(oh, ow);
         hipLaunchKernelGGL(shot_pair_k, dim3(n - 1), dim3(256), 0, c->stream, d_gray, oh, ow, t, plan, d_scratch, stride, d_dfd, d_flow);
         HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(dfd, d_dfd, (size_t)(n - 1) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (dfd) HIP_CHECK(hipMemcpyAsync(dfd, d_dfd, (size_t)(n - 1) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (motion_rows) {
+            int64_t* d_rows = sMotion.in(c->s_misc);
+            motion_fit_device(c, d_flow, n - 1, oh, ow, d_dfd, d_rows);
+            HIP_CHECK(hipMemcpyAsync(motion_rows, d_rows, sMotion.bytes(), hipMemcpyDeviceToHost, c->stream));
+        }
         if (flow_out) HIP_CHECK(hipMemcpyAsync(flow_out, d_flow, flow_bytes, hipMemcpyDeviceToHost, c->stream));
     }
     if (gray_out) HIP_CHECK(hipMemcpyAsync(gray_out, d_gray, (size_t)n * px, hipMemcpyDeviceToHost, c->stream));

@@ -154,6 +154,9 @@ _SIGS = {
     # the blend and transition verbs (BLEND.md): a frame's blend record, from resident frames or from luma planes of the caller's
     "pvf_frame_blend": (C.c_int32, [H, P, C.c_int32, C.c_int32, C.c_int32, P, C.c_int32, P, P]),
     "pvf_blend_measure": (C.c_int32, [H, P, C.c_int32, C.c_int32, C.c_int32, P]),
+    # the motion and camera verbs (MOTION.md): the motion row of a pair's flow, from flows of the caller's or from resident frames
+    "pvf_flow_motion": (C.c_int32, [H, P, C.c_int32, C.c_int32, C.c_int32, P]),
+    "pvf_shot_motion": (C.c_int32, [H, P, C.c_int32, C.c_int32, C.c_int32, P, P, P]),
     "pvf_format_rows": (C.c_int32, [P, P, P, C.c_int64, C.c_int32, C.c_int32, P, C.c_int64, P]),
     "pvf_round_rows": (C.c_int32, [P, C.c_int64, C.c_int32, P]),
     "pvf_parse_rows": (C.c_int32, [C.c_char_p, C.c_int64, P, C.c_int64, P, P]),

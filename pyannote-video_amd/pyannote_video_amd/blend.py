@@ -11,7 +11,7 @@ ABSENT = 0xFFFFFFFF                      # a sum whose earlier frame does not ex
 MAX_PIXELS = 16384                       # PVF_BLEND_MAX_PIXELS
 HISTORY = 32                             # PVF_BLEND_MAX_HISTORY
 WORDS = 16
-KINDS = ("dissolve", "fade-out", "fade-in", "blank")
+KINDS = ("dissolve", "fade-out", "fade-in", "blank", "camera")       # camera: with `transition --motion` only
 
 
 def half_up(x):
@@ -113,8 +113,9 @@ def flat_runs(flat):
     return out
 
 
-def analyse(rows, move=4.0, linear=0.25, flat=2.0, min_duration=0.12):
-    """-> ([(kind, s, e)] in row indices by (s, e, kind), the cut rows of --refined)"""
+def analyse(rows, move=4.0, linear=0.25, flat=2.0, min_duration=0.12, moving=None):
+    """-> ([(kind, s, e)] in row indices by (s, e, kind), the cut rows of --refined).  moving: the frame indices (word 13) that lie inside a
+    pan, tilt or zoom (motion.moving_frames): a span with more than half of its frames among them is a `camera` span and cuts nothing."""
     move16, lin256, flat16 = half_up(16.0 * move), half_up(256.0 * linear), half_up(16.0 * flat)
     if move16 < 1 or lin256 < 0 or flat16 < 0:
         raise ValueError("transition: --move is above 0, --linear and --flat are not negative")
@@ -130,7 +131,11 @@ def analyse(rows, move=4.0, linear=0.25, flat=2.0, min_duration=0.12):
         if t_ms[e] - t_ms[s] < long_enough:
             continue
         kind = "fade-out" if is_flat[e] and not is_flat[s] else "fade-in" if is_flat[s] and not is_flat[e] else "dissolve"
+        if moving is not None and 2 * sum(1 for r in range(s, e + 1) if int(rows[r, 13]) in moving) > e - s + 1:
+            kind = "camera"
         found.append((kind, s, e))
+        if kind == "camera":
+            continue
         if kind == "dissolve":
             cuts.add((s + e) // 2)
         else:

@@ -29,7 +29,10 @@
                                          <output.json> <prints.npy> [<prints.npy> ...]
     python -m pyannote_video_amd blend   [--width 64] [--from 0] [--until T] [--batch 64] <video> <blend.npy>
     python -m pyannote_video_amd transition [--move 4.0] [--linear 0.25] [--flat 2.0] [--min-duration 0.12] [--shots IN --refined OUT]
-                                         <blend.npy> <output.json>
+                                         [--motion motion.npy] <blend.npy> <output.json>
+    python -m pyannote_video_amd motion  [--width 96] [--from 0] [--until T] [--batch 256] <video> <motion.npy>
+    python -m pyannote_video_amd camera  [--pan 5] [--zoom 3] [--window 0.5] [--min-inliers 50] [--min-duration 0.5] [--max-gap 0.2]
+                                         [--shots shot.json] <motion.npy> <output.json>
 
 `track` and `extract` take the reference's arguments and options and write byte-compatible files (track.txt, landmarks.txt,
 embedding.txt: formats.py).  `cluster` is the verb BASELINE.json's north_star names; the reference offers clustering through the API
@@ -65,12 +68,16 @@ the titles, a rerun -- as JSON.  The thresholds are untuned; the runs and segmen
 4, 8, 16 and 32 before it, and how far the frame in the middle lies off the line between the two, summed on the GPU -- as a uint32 [n][16]
 `.npy`; `transition` reads that file alone and writes the fades, dissolves and blank stretches it shows as JSON and, with --shots and
 --refined, the shots of `shot` cut at them, which `track`, `thread` and `storyboard` read unchanged.  The thresholds are untuned.
+`motion` (no reference verb; MOTION.md) fits a similarity -- translation, zoom, roll -- to the dense flow the shot detector computes between
+every two consecutive frames, on the GPU and in integers, and writes 80 bytes a frame as an int64 [n][10] `.npy`; `camera` reads that file
+alone and writes the pans, tilts, zooms and static stretches it shows as JSON.  `transition --motion` marks the spans that lie inside a
+camera move as `camera` instead of a dissolve.  The thresholds are untuned.
 
 <video>: no codec is linked (reference video.py:345-406 runs ffmpeg); the verbs read what a decoder writes --
   * a YUV4MPEG2 file (`.y4m`, or any file that starts with `YUV4MPEG2`): 8-bit 4:2:0 / 4:2:2 / 4:4:4, memory mapped, frame rate from
     its header (`ffmpeg -i film.mkv -pix_fmt yuv420p -f yuv4mpegpipe film.y4m`); the planes go to the GPU as they are and are
     converted to RGB there (--matrix 601|709, --range limited|full override the header);
-  * `-`: the same stream from stdin, for the verbs that read the video once and need no length (`track`, `process`, `talk`, `fingerprint`, `blend`):
+  * `-`: the same stream from stdin, for the verbs that read the video once and need no length (`track`, `process`, `talk`, `fingerprint`, `blend`, `motion`):
     `ffmpeg -i film.mkv -pix_fmt yuv420p -f yuv4mpegpipe - | python -m pyannote_video_amd process - ...`;
   * a `.npy` file holding uint8 [N, H, W, 3] RGB frames (memory mapped; frame rate from --fps);
   * the bench's synthetic clip: `synthetic:<width>x<height>x<frames>[:shots[:faces[:seed]]]`.
@@ -646,15 +653,21 @@ def blend(video, output, width=64, t_from=0.0, t_until=None, batch=64, ctx=None,
     return {"frames": int(len(rows)), "first": first, "tw": tw, "th": th}
 
 
-def transition(rows, output, move=4.0, linear=0.25, flat=2.0, min_duration=0.12, shots=None, refined=None):
+def transition(rows, output, move=4.0, linear=0.25, flat=2.0, min_duration=0.12, shots=None, refined=None, motion=None):
     """Fades, dissolves and blank stretches from a blend file (BLEND.md), on the host: a JSON list of {kind, start, end, first, last}.
     With `shots` (what `shot` wrote) and `refined`, also the Timeline of `shot` cut at the middle of every dissolve and of every blank
-    run a fade ends in or starts from.  The video is not opened.  Returns the list."""
+    run a fade ends in or starts from.  With `motion` (what `motion` wrote for the same video), a span with more than half of its frames
+    inside a pan, tilt or zoom of `camera`'s default rules is written as `camera` and cuts nothing.  The video is not opened.  Returns
+    the list."""
     from . import blend as _blend
     if (shots is None) != (refined is None):
         raise ValueError("transition: --shots and --refined go together")
     table = _blend.load(rows) if isinstance(rows, str) else np.ascontiguousarray(rows)
-    found, cuts = _blend.analyse(table, move=move, linear=linear, flat=flat, min_duration=min_duration)
+    more = {}
+    if motion is not None:
+        from . import motion as _motion
+        more["moving"] = _motion.moving_frames(_motion.load(motion, "transition") if isinstance(motion, str) else np.ascontiguousarray(motion))
+    found, cuts = _blend.analyse(table, move=move, linear=linear, flat=flat, min_duration=min_duration, **more)
     listed = _blend.report(table, found)
     text = json.dumps(listed, indent=1)
     if str(output) == "-":
@@ -668,6 +681,83 @@ def transition(rows, output, move=4.0, linear=0.25, flat=2.0, min_duration=0.12,
         pieces = _blend.refine(before, [int(table[c, 12]) / 1000.0 for c in cuts])
         with open(refined, "w") as fp:
             json.dump({"pyannote": "Timeline", "content": [{"start": a, "end": b} for a, b in pieces]}, fp)
+    return listed
+
+
+def motion(video, output, width=96, t_from=0.0, t_until=None, batch=256, ctx=None, ahead=96):
+    """The motion row of every frame of the video whose time lies in [t_from, t_until) (MOTION.md): one streaming pass as `blend` makes
+    it.  The small image is `width` pixels wide and keeps the frame's aspect: the shot detector's gray, bilinear image, of which the
+    library computes the dense flow between every two consecutive frames and fits the camera's motion to it.  `batch` resident frames
+    per shot_motion call; a batch's last frame stays resident as the first frame of the next call (motion.Pairs), so the file does not
+    depend on `batch`.  The first frame of the range has no frame before it and gets a row without valid pixels.  Writes int64 [n][10],
+    stamped with ms(T) | index << 32, as a .npy file (`output` may be an open binary file).  Returns {"frames", "first", "tw", "th"}."""
+    from . import motion as _motion, repeat as _repeat, runtime
+    from .feed import FrameFeed
+    if int(batch) < 1:
+        raise ValueError("motion: a batch holds at least one frame")
+    if int(width) < 1:
+        raise ValueError("motion: --width is at least 1")
+    rate = float(video.frame_rate)
+    w, h = video.frame_size
+    tw, th = _motion.tile_size(width, w, h)
+    first = 0
+    while first / rate < t_from:
+        first += 1
+    end = None
+    if t_until is not None:
+        end = first
+        while end / rate < t_until:
+            end += 1
+    try:
+        end = len(video) if end is None else min(end, len(video))
+    except TypeError:                        # a stream: as far as it goes
+        pass
+    ctx = ctx or runtime.default_context()
+    pairs = _motion.Pairs(ctx, tw, th)
+    parts, pend = [], []
+    with FrameFeed(ctx, video, _repeat.EveryFrame(first, end), ahead=max(ahead, 2 * int(batch)), name="pvface-motion-reader") as feed:
+        def flush():
+            rows, done = pairs.measure(pend)
+            parts.append(rows)
+            feed.release_all(pend[:-1])          # the last one is the next call's first frame
+            if done is not None:
+                feed.release(done)
+            del pend[:]
+        for _, dev in feed:
+            pend.append(dev)
+            if len(pend) >= batch:
+                flush()
+        if pend:
+            flush()
+        if pairs.held is not None:
+            feed.release(pairs.held)
+    rows = _motion.stamp(np.concatenate(parts) if parts else np.zeros((0, _motion.WORDS), np.int64), first, rate)
+    if hasattr(output, "write"):
+        np.save(output, rows)
+    else:
+        with open(output, "wb") as fo:
+            np.save(fo, rows)
+    return {"frames": int(len(rows)), "first": first, "tw": tw, "th": th}
+
+
+def camera(rows, output, pan=5.0, zoom=3.0, window=0.5, min_inliers=50, min_duration=0.5, max_gap=0.2, shots=None):
+    """Pans, tilts, zooms and static stretches from a motion file (MOTION.md), on the host: a JSON list of {kind, start, end, first, last,
+    rate}.  With `shots` (what `shot` wrote) no pair that straddles a shot boundary counts and no span crosses one.  The video is not
+    opened.  Returns the list."""
+    from . import motion as _motion
+    table = _motion.load(rows) if isinstance(rows, str) else np.ascontiguousarray(rows)
+    if shots is not None:
+        shots = [(s.start, s.end) for s in (load_shots(shots) if isinstance(shots, str) else shots)]
+    found = _motion.analyse(table, pan=pan, zoom=zoom, window=window, min_inliers=min_inliers, min_duration=min_duration, max_gap=max_gap,
+                            shots=shots)
+    listed = _motion.report(table, found)
+    text = json.dumps(listed, indent=1)
+    if str(output) == "-":
+        sys.stdout.write(text + "\n")
+        sys.stdout.flush()
+    else:
+        with open(output, "w") as fo:
+            fo.write(text + "\n")
     return listed
 
 
@@ -1100,6 +1190,22 @@ def _parser():
     tr.add_argument("--min-duration", type=float, default=0.12, help="shorter spans and blank runs are dropped, seconds")
     tr.add_argument("--shots", default=None, help="what `shot` wrote: with --refined, the shots cut at the transitions")
     tr.add_argument("--refined", default=None, help="where the refined Timeline is written")
+    tr.add_argument("--motion", default=None, help="what `motion` wrote for the same video: spans inside a pan, tilt or zoom are written as `camera`")
+    mo = sub.add_parser("motion", help="the camera motion between every two consecutive frames of a video, as an int64 [n][10] .npy file")
+    mo.add_argument("video"); mo.add_argument("output", help="the .npy path the rows are written to")
+    mo.add_argument("--width", type=int, default=96, help="width of the small image the flow is computed on; the height keeps the frame's aspect")
+    mo.add_argument("--from", dest="t_from", type=float, default=0.0, help="frames from this time on, seconds")
+    mo.add_argument("--until", dest="t_until", type=float, default=None, help="frames before this, seconds")
+    mo.add_argument("--batch", type=int, default=256, help="frames measured per library call, and resident at a time")
+    ca = sub.add_parser("camera", help="pans, tilts, zooms and static stretches from a motion file of `motion`, as JSON; the video is not opened")
+    ca.add_argument("rows", help="the motion file"); ca.add_argument("output", help="a path, or - for stdout")
+    ca.add_argument("--pan", type=float, default=5.0, help="least pan or tilt, percent of the frame's side per second")
+    ca.add_argument("--zoom", type=float, default=3.0, help="least zoom, percent of scale per second")
+    ca.add_argument("--window", type=float, default=0.5, help="seconds the rates are averaged over, centred on the frame")
+    ca.add_argument("--min-inliers", type=int, default=50, help="least share of a pair's pixels the model must hold, percent")
+    ca.add_argument("--min-duration", type=float, default=0.5, help="shorter spans are dropped, seconds")
+    ca.add_argument("--max-gap", type=float, default=0.2, help="runs of one label this close are one span, seconds")
+    ca.add_argument("--shots", default=None, help="what `shot` wrote: pairs across a boundary do not count, spans do not cross one")
     c = sub.add_parser("cluster")
     c.add_argument("embeddings"); c.add_argument("labels")
     c.add_argument("--threshold", type=float, default=0.6)
@@ -1240,7 +1346,7 @@ def main(argv=None):
         if a.video == "-" and a.verb == "faces":
             ap.error("faces reads the video twice, once for the quality of every face and once for the frames of the chosen ones: "
                      "give it a file, not a stream on stdin")
-        if a.video == "-" and a.verb not in ("track", "process", "talk", "tube", "fingerprint", "blend"):
+        if a.video == "-" and a.verb not in ("track", "process", "talk", "tube", "fingerprint", "blend", "motion"):
             ap.error("%s needs the length of the video: give it a file, not a stream on stdin" % a.verb)
         over = {}
         if a.matrix is not None:
@@ -1316,7 +1422,21 @@ def main(argv=None):
             ap.error(str(e))
     elif a.verb == "transition":
         try:
-            transition(a.rows, a.output, move=a.move, linear=a.linear, flat=a.flat, min_duration=a.min_duration, shots=a.shots, refined=a.refined)
+            transition(a.rows, a.output, move=a.move, linear=a.linear, flat=a.flat, min_duration=a.min_duration, shots=a.shots, refined=a.refined,
+                       motion=a.motion)
+        except ValueError as e:
+            ap.error(str(e))
+    elif a.verb == "motion":
+        if a.batch < 1 or a.width < 1:
+            ap.error("--batch and --width are at least 1")
+        try:
+            res = motion(video(), a.output, width=a.width, t_from=a.t_from, t_until=a.t_until, batch=a.batch, ctx=ctx)
+        except ValueError as e:
+            ap.error(str(e))
+    elif a.verb == "camera":
+        try:
+            camera(a.rows, a.output, pan=a.pan, zoom=a.zoom, window=a.window, min_inliers=a.min_inliers, min_duration=a.min_duration,
+                   max_gap=a.max_gap, shots=a.shots)
         except ValueError as e:
             ap.error(str(e))
     elif a.verb == "demo":

@@ -1225,6 +1225,30 @@ class Context(object):
         check(self._l.pvf_blend_measure(self._h, ptr(luma) if luma.size else None, N, P, int(first), ptr(rows) if rows.size else None))
         return rows
 
+    def flow_motion(self, flow):
+        """-> int64 [n, 10]: the motion rows (MOTION.md) of the caller's own flows float32 [n, h, w, 2] (pvf_flow_motion); word 7 is 0"""
+        flow = np.ascontiguousarray(flow, np.float32)
+        if flow.ndim != 4 or flow.shape[3] != 2:
+            raise ValueError("flow_motion: the flows are float32 [n, h, w, 2]")
+        n, h, w = flow.shape[:3]
+        rows = np.zeros((n, 10), np.int64)
+        check(self._l.pvf_flow_motion(self._h, ptr(flow) if flow.size else None, n, h, w, ptr(rows) if n else None))
+        return rows
+
+    def shot_motion(self, frames, width, height, tables, want_dfd=True):
+        """resident frames of one size -> (rows int64 [n - 1, 10], dfd float64 [n - 1] or None): the motion rows of the flows
+        pvf_shot_dfd computes between consecutive frames, fitted on the device (pvf_shot_motion); word 7 holds the bits of dfd"""
+        n = len(frames)
+        t = np.ascontiguousarray(tables, np.float32)
+        if t.shape != (22,):
+            raise ValueError("shot tables: 22 floats (structure.shot_tables())")
+        rows = np.zeros((max(n - 1, 0), 10), np.int64)
+        dfd = np.zeros(max(n - 1, 0), np.float64) if want_dfd else None
+        with self._staging():
+            check(self._l.pvf_shot_motion(self._h, ptr(self._handles(frames)) if n else None, n, int(width), int(height), ptr(t),
+                                          ptr(rows) if n > 1 else None, ptr(dfd) if want_dfd and n > 1 else None))
+        return rows, dfd
+
     # The four agglomerating calls have a `_cooccur` sibling that takes `extent` (float64 [T, 2]: start and end of every track, seconds):
     # the do-not-cooccur constraint (clustering.py:142-143; pvf_cluster_*_cooccur) -- tracks whose extents intersect never share a
     # cluster.  They return (labels, merge log, n_blocked = the co-occurring pairs); `flags` bit 0 is the library's test switch
