@@ -672,6 +672,27 @@ int32_t pvf_flow_motion(pvf_handle ctx, const float* flow /* n_pairs*h*w*2, host
 int32_t pvf_shot_motion(pvf_handle ctx, const pvf_handle* frames, int32_t n, int32_t width, int32_t height, const float* tables,
                         int64_t* rows /* (n-1)*10, host */, double* dfd /* n-1 host, or NULL */);
 
+/* ---- overlaid text: the text record of a frame (CAPTION.md; no reference call) ------------------------------------------------------
+ * On the luma Y = (77 R + 150 G + 29 B + 128) >> 8 of a resident h x w frame at full resolution, a pixel is a stroke pixel when the central
+ * horizontal difference |Y(min(x + 1, w - 1), y) - Y(max(x - 1, 0), y)| is at least `edge`.  Per cell of PVF_TEXT_CELL x PVF_TEXT_CELL
+ * pixels (cw = ceil(w / 16) by ch = ceil(h / 16); the right and lower cells may be partial): NP pixels inside the frame, E stroke pixels,
+ * S stroke pixels that are stroke pixels of the predecessor too with |Y - Y_p| <= still, M pixels with |Y - Y_p| > still; without a
+ * predecessor S = M = 0.  The predecessor of frames[i] is frames[i - 1], of frames[0] it is `prev` (0: none).  A row is uint32
+ * [PVF_TEXT_HEAD_WORDS + ch * wpr], wpr = ceil(cw / 32): w | h << 16; edge | still << 8 | on << 16 | has_prev << 31; the sums of E, S and M
+ * over the cells; the number of set bits; two words of the caller's (written as 0); then the mask, cell row r in words 8 + r * wpr ..,
+ * cell c bit c & 31 of word c >> 5, the bit S >= on, bits at c >= cw 0.  counts, when not NULL, receives E, S, M, NP of every cell.
+ * The call keeps no state: the caller hands the last frame of a batch in again as `prev` of the next.  n = 0 does nothing.
+ * Refused before any work: n negative or beyond PVF_TEXT_MAX_FRAMES, edge outside 1 .. 255, still outside 0 .. 254, on outside
+ * 1 .. 256, null frames or rows, an unknown or released frame (prev included), frames of different sizes, a side beyond PVF_TEXT_MAX_SIDE. */
+#define PVF_TEXT_CELL 16
+#define PVF_TEXT_HEAD_WORDS 8
+#define PVF_TEXT_MAX_SIDE 8192
+#define PVF_TEXT_MAX_FRAMES 4096
+int32_t pvf_frame_text(pvf_handle ctx, const pvf_handle* frames, int32_t n, pvf_handle prev /* or 0 */,
+                       int32_t edge, int32_t still, int32_t on,
+                       uint32_t* rows   /* n * (8 + ch*wpr), host */,
+                       uint16_t* counts /* n*ch*cw*4 = E, S, M, NP; host, or NULL */);
+
 /* ---- file formats (host) ------------------------------------------------------------------------------ */
 /* ref: scripts/pyannote-face.py:299-311  the lines of landmarks.txt / embedding.txt: "{t:.3f} {identifier:d}" + n_cols x " {v:.<decimals>f}"
  * + newline per row, byte for byte what Python's format writes (both are the correctly rounded decimal).  values [n_rows][n_cols];

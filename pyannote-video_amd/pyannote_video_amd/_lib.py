@@ -157,6 +157,8 @@ _SIGS = {
     # the motion and camera verbs (MOTION.md): the motion row of a pair's flow, from flows of the caller's or from resident frames
     "pvf_flow_motion": (C.c_int32, [H, P, C.c_int32, C.c_int32, C.c_int32, P]),
     "pvf_shot_motion": (C.c_int32, [H, P, C.c_int32, C.c_int32, C.c_int32, P, P, P]),
+    # the text and caption verbs (CAPTION.md): the text record of resident frames at full resolution
+    "pvf_frame_text": (C.c_int32, [H, P, C.c_int32, H, C.c_int32, C.c_int32, C.c_int32, P, P]),
     "pvf_format_rows": (C.c_int32, [P, P, P, C.c_int64, C.c_int32, C.c_int32, P, C.c_int64, P]),
     "pvf_round_rows": (C.c_int32, [P, C.c_int64, C.c_int32, P]),
     "pvf_parse_rows": (C.c_int32, [C.c_char_p, C.c_int64, P, C.c_int64, P, P]),

@@ -33,6 +33,9 @@
     python -m pyannote_video_amd motion  [--width 96] [--from 0] [--until T] [--batch 256] <video> <motion.npy>
     python -m pyannote_video_amd camera  [--pan 5] [--zoom 3] [--window 0.5] [--min-inliers 50] [--min-duration 0.5] [--max-gap 0.2]
                                          [--shots shot.json] <motion.npy> <output.json>
+    python -m pyannote_video_amd text    [--step 0] [--edge 48] [--still 8] [--on 24] [--from 0] [--until T] [--batch 64] <video> <text.npy>
+    python -m pyannote_video_amd caption [--window 1.0] [--hold 0.5] [--gap 1] [--min-duration 1.0] [--min-width 3] [--max-height 0.25]
+                                         [--fill 0.5] [--rows 0,1] [--tracking PATH] <text.npy> <output.json>
 
 `track` and `extract` take the reference's arguments and options and write byte-compatible files (track.txt, landmarks.txt,
 embedding.txt: formats.py).  `cluster` is the verb BASELINE.json's north_star names; the reference offers clustering through the API
@@ -72,12 +75,17 @@ the titles, a rerun -- as JSON.  The thresholds are untuned; the runs and segmen
 every two consecutive frames, on the GPU and in integers, and writes 80 bytes a frame as an int64 [n][10] `.npy`; `camera` reads that file
 alone and writes the pans, tilts, zooms and static stretches it shows as JSON.  `transition --motion` marks the spans that lie inside a
 camera move as `camera` instead of a dissolve.  The thresholds are untuned.
+`text` (no reference verb; CAPTION.md) measures overlaid text -- name straps, subtitles, title cards -- on every pixel of every frame at
+full resolution, on the GPU and in integers: per 16 x 16 cell the pixels with a strong horizontal luma difference that were there, unmoved,
+in the frame before, and one mask bit a cell, as a uint32 [n][8 + ch wpr] `.npy`; `caption` reads that file alone and writes the
+captions it shows -- when, and in which box of the picture -- as JSON, with --tracking also the tracks on screen with each.  No
+characters are read.  The thresholds are untuned.
 
 <video>: no codec is linked (reference video.py:345-406 runs ffmpeg); the verbs read what a decoder writes --
   * a YUV4MPEG2 file (`.y4m`, or any file that starts with `YUV4MPEG2`): 8-bit 4:2:0 / 4:2:2 / 4:4:4, memory mapped, frame rate from
     its header (`ffmpeg -i film.mkv -pix_fmt yuv420p -f yuv4mpegpipe film.y4m`); the planes go to the GPU as they are and are
     converted to RGB there (--matrix 601|709, --range limited|full override the header);
-  * `-`: the same stream from stdin, for the verbs that read the video once and need no length (`track`, `process`, `talk`, `fingerprint`, `blend`, `motion`):
+  * `-`: the same stream from stdin, for the verbs that read the video once and need no length (`track`, `process`, `talk`, `fingerprint`, `blend`, `motion`, `text`):
     `ffmpeg -i film.mkv -pix_fmt yuv420p -f yuv4mpegpipe - | python -m pyannote_video_amd process - ...`;
   * a `.npy` file holding uint8 [N, H, W, 3] RGB frames (memory mapped; frame rate from --fps);
   * the bench's synthetic clip: `synthetic:<width>x<height>x<frames>[:shots[:faces[:seed]]]`.
@@ -761,6 +769,86 @@ def camera(rows, output, pan=5.0, zoom=3.0, window=0.5, min_inliers=50, min_dura
     return listed
 
 
+def text(video, output, step=0.0, edge=48, still=8, on=24, t_from=0.0, t_until=None, batch=64, ctx=None, ahead=96):
+    """The text record of the frames of the video whose time lies in [t_from, t_until) (CAPTION.md): one streaming pass as `blend` makes
+    it, at full resolution.  Every k-th frame from the first is measured, k = max(1, floor(step * rate + 1 / 2)), against the measured
+    frame before it.  `batch` resident frames per frame_text call; a batch's last frame stays resident as `prev` of the next call
+    (text.Carry), so the file does not depend on `batch`.  Writes uint32 [n][8 + ch wpr], stamped with ms(T) and the frame index, as a
+    .npy file (`output` may be an open binary file).  Returns {"frames", "first", "every"}."""
+    from . import text as _text, runtime
+    from .feed import FrameFeed
+    if not 1 <= int(batch) <= _text.MAX_FRAMES:
+        raise ValueError("text: a batch holds 1 .. %d frames" % _text.MAX_FRAMES)
+    if step < 0:
+        raise ValueError("text: --step is not negative")
+    rate = float(video.frame_rate)
+    w, h = video.frame_size
+    if not (1 <= w <= _text.MAX_SIDE and 1 <= h <= _text.MAX_SIDE):
+        raise ValueError("text: frames of %d x %d; sides of at most %d are measured" % (w, h, _text.MAX_SIDE))
+    k = _text.every(step, rate)
+    first = 0
+    while first / rate < t_from:
+        first += 1
+    end = None
+    if t_until is not None:
+        end = first
+        while end / rate < t_until:
+            end += 1
+    try:
+        end = len(video) if end is None else min(end, len(video))
+    except TypeError:                        # a stream: as far as it goes
+        pass
+    ctx = ctx or runtime.default_context()
+    carry = _text.Carry(ctx, edge=edge, still=still, on=on)
+    parts, pend = [], []
+    with FrameFeed(ctx, video, _text.EveryKth(first, end, k), ahead=max(ahead, 2 * int(batch)), name="pvface-text-reader") as feed:
+        def flush():
+            rows, done = carry.measure(pend)
+            parts.append(rows)
+            feed.release_all(pend[:-1])          # the last one is the next call's prev
+            if done is not None:
+                feed.release(done)
+            del pend[:]
+        for _, dev in feed:
+            pend.append(dev)
+            if len(pend) >= batch:
+                flush()
+        if pend:
+            flush()
+        if carry.held is not None:
+            feed.release(carry.held)
+    rows = _text.stamp(np.concatenate(parts) if parts else np.zeros((0, _text.row_words(w, h)), np.uint32), first, rate, k)
+    if hasattr(output, "write"):
+        np.save(output, rows)
+    else:
+        with open(output, "wb") as fo:
+            np.save(fo, rows)
+    return {"frames": int(len(rows)), "first": first, "every": k}
+
+
+def caption(rows, output, window=1.0, hold=0.5, gap=1, min_duration=1.0, min_width=3, max_height=0.25, fill=0.5, band=(0.0, 1.0), tracking=None):
+    """Captions from a text file (CAPTION.md), on the host: a JSON list of {start, end, first, last, left, top, right, bottom, cells}, the
+    box in pixels.  With `tracking` (what `track` wrote) every caption also lists the `tracks` on screen for at least half of it and
+    whether one is `alone`.  The video is not opened.  Returns the list."""
+    from . import text as _text
+    table = _text.load(rows) if isinstance(rows, str) else _text.check(np.asarray(rows))
+    tracks = None
+    if tracking is not None:
+        from . import formats
+        tracks = formats.read_tracks(tracking) if isinstance(tracking, str) else tracking
+    found = _text.analyse(table, window=window, hold=hold, gap=gap, min_duration=min_duration, min_width=min_width, max_height=max_height,
+                          fill=fill, band=band)
+    listed = _text.report(table, found, tracks)
+    out = json.dumps(listed, indent=1)
+    if str(output) == "-":
+        sys.stdout.write(out + "\n")
+        sys.stdout.flush()
+    else:
+        with open(output, "w") as fo:
+            fo.write(out + "\n")
+    return listed
+
+
 def demo(video, tracking, output, height=400, t_from=0.0, t_until=None, shift=0.0, landmark=None, label=None, matrix="601",
          full_range=False, fps=None, ctx=None, ring_depth=16):
     """Annotated video (pyannote-face.py:317-413) as YUV4MPEG2, to a path or to stdout (`-`).  What is drawn on which frame is planned
@@ -1206,6 +1294,26 @@ def _parser():
     ca.add_argument("--min-duration", type=float, default=0.5, help="shorter spans are dropped, seconds")
     ca.add_argument("--max-gap", type=float, default=0.2, help="runs of one label this close are one span, seconds")
     ca.add_argument("--shots", default=None, help="what `shot` wrote: pairs across a boundary do not count, spans do not cross one")
+    tx = sub.add_parser("text", help="overlaid text per 16 x 16 cell of every frame at full resolution, as a uint32 [n][8 + ch wpr] .npy file")
+    tx.add_argument("video"); tx.add_argument("output", help="the .npy path the rows are written to")
+    tx.add_argument("--step", type=float, default=0.0, help="seconds between measured frames; 0: every frame")
+    tx.add_argument("--edge", type=int, default=48, help="least horizontal luma difference of a stroke pixel, 1 .. 255")
+    tx.add_argument("--still", type=int, default=8, help="largest luma change of a pixel that has not moved, 0 .. 254")
+    tx.add_argument("--on", type=int, default=24, help="persistent stroke pixels that set a cell's bit, 1 .. 256")
+    tx.add_argument("--from", dest="t_from", type=float, default=0.0, help="frames from this time on, seconds")
+    tx.add_argument("--until", dest="t_until", type=float, default=None, help="frames before this, seconds")
+    tx.add_argument("--batch", type=int, default=64, help="frames measured per library call, and resident at a time")
+    cp = sub.add_parser("caption", help="name straps, subtitles and title cards from a text file of `text`, as JSON; the video is not opened")
+    cp.add_argument("rows", help="the text file"); cp.add_argument("output", help="a path, or - for stdout")
+    cp.add_argument("--window", type=float, default=1.0, help="seconds a cell is voted over, centred on the frame")
+    cp.add_argument("--hold", type=float, default=0.5, help="least share of the window's frames with the cell's bit set, 0 .. 1")
+    cp.add_argument("--gap", type=int, default=1, help="unheld cells between two held ones of a cell row that are closed: the spaces between words")
+    cp.add_argument("--min-duration", type=float, default=1.0, help="shorter captions are dropped, seconds")
+    cp.add_argument("--min-width", type=int, default=3, help="narrower captions are dropped, cells")
+    cp.add_argument("--max-height", type=float, default=0.25, help="taller captions are dropped, share of the frame's height")
+    cp.add_argument("--fill", type=float, default=0.5, help="least share of its box, over its frames, a caption fills, 0 .. 1")
+    cp.add_argument("--rows", dest="band", default="0,1", help="A,B: only the cell rows whose centre lies in [A, B) of the frame's height")
+    cp.add_argument("--tracking", default=None, help="what `track` wrote: the tracks on screen with each caption")
     c = sub.add_parser("cluster")
     c.add_argument("embeddings"); c.add_argument("labels")
     c.add_argument("--threshold", type=float, default=0.6)
@@ -1346,7 +1454,7 @@ def main(argv=None):
         if a.video == "-" and a.verb == "faces":
             ap.error("faces reads the video twice, once for the quality of every face and once for the frames of the chosen ones: "
                      "give it a file, not a stream on stdin")
-        if a.video == "-" and a.verb not in ("track", "process", "talk", "tube", "fingerprint", "blend", "motion"):
+        if a.video == "-" and a.verb not in ("track", "process", "talk", "tube", "fingerprint", "blend", "motion", "text"):
             ap.error("%s needs the length of the video: give it a file, not a stream on stdin" % a.verb)
         over = {}
         if a.matrix is not None:
@@ -1437,6 +1545,20 @@ def main(argv=None):
         try:
             camera(a.rows, a.output, pan=a.pan, zoom=a.zoom, window=a.window, min_inliers=a.min_inliers, min_duration=a.min_duration,
                    max_gap=a.max_gap, shots=a.shots)
+        except ValueError as e:
+            ap.error(str(e))
+    elif a.verb == "text":
+        try:
+            res = text(video(), a.output, step=a.step, edge=a.edge, still=a.still, on=a.on, t_from=a.t_from, t_until=a.t_until, batch=a.batch, ctx=ctx)
+        except ValueError as e:
+            ap.error(str(e))
+    elif a.verb == "caption":
+        try:
+            band = tuple(float(v) for v in a.band.split(","))
+            if len(band) != 2:
+                raise ValueError("caption: --rows A,B with 0 <= A < B <= 1")
+            caption(a.rows, a.output, window=a.window, hold=a.hold, gap=a.gap, min_duration=a.min_duration, min_width=a.min_width,
+                    max_height=a.max_height, fill=a.fill, band=band, tracking=a.tracking)
         except ValueError as e:
             ap.error(str(e))
     elif a.verb == "demo":

@@ -1249,6 +1249,22 @@ class Context(object):
                                           ptr(rows) if n > 1 else None, ptr(dfd) if want_dfd and n > 1 else None))
         return rows, dfd
 
+    def frame_text(self, frames, prev=None, edge=48, still=8, on=24, want_counts=False, size=None):
+        """resident frames of one size as text records (pvf_frame_text; CAPTION.md): (rows uint32 [n, 8 + ch * wpr], counts uint16
+        [n, ch, cw, 4] = E, S, M, NP or None).  prev: the resident frame in front of frames[0] -- the last frame of the call before;
+        the call keeps nothing.  size: (w, h), needed only where `frames` are bare handles (frame_handles)."""
+        n = len(frames)
+        if n == 0:
+            return np.zeros((0, 8), np.uint32), (np.zeros((0, 0, 0, 4), np.uint16) if want_counts else None)
+        w, h = size if size is not None else (frames[0].shape[1], frames[0].shape[0])
+        cw, ch = (w + 15) // 16, (h + 15) // 16
+        rows = np.zeros((n, 8 + ch * ((cw + 31) // 32)), np.uint32)
+        counts = np.zeros((n, ch, cw, 4), np.uint16) if want_counts else None
+        with self._staging():
+            check(self._l.pvf_frame_text(self._h, ptr(self._handles(frames)), n, int(getattr(prev, "handle", prev)) if prev is not None else 0, int(edge), int(still),
+                                         int(on), ptr(rows), ptr(counts) if want_counts else None))
+        return rows, counts
+
     # The four agglomerating calls have a `_cooccur` sibling that takes `extent` (float64 [T, 2]: start and end of every track, seconds):
     # the do-not-cooccur constraint (clustering.py:142-143; pvf_cluster_*_cooccur) -- tracks whose extents intersect never share a
     # cluster.  They return (labels, merge log, n_blocked = the co-occurring pairs); `flags` bit 0 is the library's test switch
