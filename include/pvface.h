@@ -693,6 +693,25 @@ int32_t pvf_frame_text(pvf_handle ctx, const pvf_handle* frames, int32_t n, pvf_
                        uint32_t* rows   /* n * (8 + ch*wpr), host */,
                        uint16_t* counts /* n*ch*cw*4 = E, S, M, NP; host, or NULL */);
 
+/* ---- what a person wears: colour histograms over windows of resident frames (CLOTHES.md; no reference call) -------------------------
+ * The bin of a pixel (R, G, B): Y = (77 R + 150 G + 29 B + 128) >> 8, c1 = R - G, c2 = (2 B - R - G) >> 1 (an arithmetic shift: the floor),
+ * q(c) = min(max((c + 64) >> 4, 0), 7), bin = (Y >> 6) * 64 + q(c1) * 8 + q(c2).  Window i is windows[4 i .. 4 i + 3] = (x0, y0, x1, y1)
+ * of frame frames[i]: int32 pixels, half-open, anywhere relative to the frame; only pixels inside the frame count (the clip is computed in
+ * 64 bits), x1 <= x0 or y1 <= y0 is an empty window.  Row y of a window belongs to band ((y - y0) * B) // (y1 - y0): the unclipped height.
+ * out is uint32 [G][B][256]: the counts of all pixels of all windows i with group[i] = g, per band; a group without windows is zero.
+ * Frames may differ in size within a call.  out: host memory, or with out_on_device device memory; the call is complete when it returns.
+ * n = 0 writes zeros.  Windows go through the device as pieces, in rounds (2^18 pieces, or what the environment variable PVF_HIST_ROUND
+ * names, read at the call); nothing depends on the rounds.
+ * Refused before any work: n < 0 or beyond PVF_HIST_MAX_WINDOWS, G < 1, B outside 1 .. PVF_HIST_MAX_BANDS, G * B beyond PVF_HIST_MAX_ROWS,
+ * null pointers with n > 0, a group outside 0 .. G - 1, an unknown or released frame, a group whose clipped pixels in this call number
+ * 2^32 or more (the host adds the clipped areas in 64 bits before it launches). */
+#define PVF_HIST_BINS 256
+#define PVF_HIST_MAX_BANDS 4
+#define PVF_HIST_MAX_WINDOWS 65536       /* windows of one call */
+#define PVF_HIST_MAX_ROWS 65536          /* G * B: 64 MiB of result */
+int32_t pvf_frame_hist(pvf_handle ctx, const pvf_handle* frames, const int32_t* windows /* n*4 */, const int32_t* group /* n */,
+                       int32_t n, int32_t G, int32_t B, uint32_t* out /* G*B*256 */, int32_t out_on_device);
+
 /* ---- file formats (host) ------------------------------------------------------------------------------ */
 /* ref: scripts/pyannote-face.py:299-311  the lines of landmarks.txt / embedding.txt: "{t:.3f} {identifier:d}" + n_cols x " {v:.<decimals>f}"
  * + newline per row, byte for byte what Python's format writes (both are the correctly rounded decimal).  values [n_rows][n_cols];

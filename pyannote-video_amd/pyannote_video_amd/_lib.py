@@ -159,6 +159,8 @@ _SIGS = {
     "pvf_shot_motion": (C.c_int32, [H, P, C.c_int32, C.c_int32, C.c_int32, P, P, P]),
     # the text and caption verbs (CAPTION.md): the text record of resident frames at full resolution
     "pvf_frame_text": (C.c_int32, [H, P, C.c_int32, H, C.c_int32, C.c_int32, C.c_int32, P, P]),
+    # the clothes and link verbs (CLOTHES.md): colour histograms over windows of resident frames, per group and band
+    "pvf_frame_hist": (C.c_int32, [H, P, P, P, C.c_int32, C.c_int32, C.c_int32, P, C.c_int32]),
     "pvf_format_rows": (C.c_int32, [P, P, P, C.c_int64, C.c_int32, C.c_int32, P, C.c_int64, P]),
     "pvf_round_rows": (C.c_int32, [P, C.c_int64, C.c_int32, P]),
     "pvf_parse_rows": (C.c_int32, [C.c_char_p, C.c_int64, P, C.c_int64, P, P]),

@@ -36,6 +36,10 @@
     python -m pyannote_video_amd text    [--step 0] [--edge 48] [--still 8] [--on 24] [--from 0] [--until T] [--batch 64] <video> <text.npy>
     python -m pyannote_video_amd caption [--window 1.0] [--hold 0.5] [--gap 1] [--min-duration 1.0] [--min-width 3] [--max-height 0.25]
                                          [--fill 0.5] [--rows 0,1] [--tracking PATH] <text.npy> <output.json>
+    python -m pyannote_video_amd clothes [--widen 0.5] [--drop 0.25] [--height 2.0] [--bands 2] [--min-size 0] [--keep-overlapped]
+                                         [--from 0] [--until T] [--batch 2048] <video> <tracking> <clothes.npy>
+    python -m pyannote_video_amd link    [--min-score 0.75] [--margin 0.05] [--max-gap 120] [--min-faces 3] [--min-pixels 20000]
+                                         [--labels IN --merged OUT] <clothes.npy> <output.json>
 
 `track` and `extract` take the reference's arguments and options and write byte-compatible files (track.txt, landmarks.txt,
 embedding.txt: formats.py).  `cluster` is the verb BASELINE.json's north_star names; the reference offers clustering through the API
@@ -80,12 +84,16 @@ full resolution, on the GPU and in integers: per 16 x 16 cell the pixels with a 
 in the frame before, and one mask bit a cell, as a uint32 [n][8 + ch wpr] `.npy`; `caption` reads that file alone and writes the
 captions it shows -- when, and in which box of the picture -- as JSON, with --tracking also the tracks on screen with each.  No
 characters are read.  The thresholds are untuned.
+`clothes` (no reference verb; CLOTHES.md) measures what a person wears: a colour histogram of 256 bins, summed on the GPU and in integers over
+the torso windows under the faces of every track, as an int64 [T][6 + 256 bands] `.npy`; `link` reads that file alone and writes which
+tracks wear the same clothes -- mutual best matches by histogram intersection, with a margin -- as JSON and, with --labels and --merged,
+the label file of `cluster` or `identify` merged along those links.  No body is detected.  The thresholds are untuned.
 
 <video>: no codec is linked (reference video.py:345-406 runs ffmpeg); the verbs read what a decoder writes --
   * a YUV4MPEG2 file (`.y4m`, or any file that starts with `YUV4MPEG2`): 8-bit 4:2:0 / 4:2:2 / 4:4:4, memory mapped, frame rate from
     its header (`ffmpeg -i film.mkv -pix_fmt yuv420p -f yuv4mpegpipe film.y4m`); the planes go to the GPU as they are and are
     converted to RGB there (--matrix 601|709, --range limited|full override the header);
-  * `-`: the same stream from stdin, for the verbs that read the video once and need no length (`track`, `process`, `talk`, `fingerprint`, `blend`, `motion`, `text`):
+  * `-`: the same stream from stdin, for the verbs that read the video once and need no length (`track`, `process`, `talk`, `fingerprint`, `blend`, `motion`, `text`, `clothes`):
     `ffmpeg -i film.mkv -pix_fmt yuv420p -f yuv4mpegpipe - | python -m pyannote_video_amd process - ...`;
   * a `.npy` file holding uint8 [N, H, W, 3] RGB frames (memory mapped; frame rate from --fps);
   * the bench's synthetic clip: `synthetic:<width>x<height>x<frames>[:shots[:faces[:seed]]]`.
@@ -849,6 +857,102 @@ def caption(rows, output, window=1.0, hold=0.5, gap=1, min_duration=1.0, min_wid
     return listed
 
 
+def clothes(video, tracking, output, widen=0.5, drop=0.25, height=2.0, bands=2, min_size=0.0, keep_overlapped=False, t_from=0.0, t_until=None,
+            batch=2048, ctx=None, ahead=96):
+    """What every track wears (CLOTHES.md): one pass over the frames that carry faces, as `talk` makes it without the carried frame.  The
+    torso windows (clothes.torso) of the faces whose time lies in [t_from, t_until) go through Context.frame_hist in calls of `batch`
+    windows, one group per track present in the call; the uint32 results are added into an int64 table on the host, so the file does
+    not depend on `batch`.  Writes int64 [T][6 + 256 bands], a row per track of the tracking file in ascending track number: track, ms
+    of its first and last row in the range (-1 without one), faces used, faces skipped, bands, the histogram.  Returns {"tracks",
+    "faces", "skipped"}."""
+    from . import clothes as _clothes, runtime
+    from .feed import FrameFeed
+    from .pipeline import faces_per_frame
+    from .talk import ms
+    if not 1 <= int(batch) <= _clothes.MAX_WINDOWS:
+        raise ValueError("clothes: a batch holds 1 .. %d windows" % _clothes.MAX_WINDOWS)
+    if not 1 <= int(bands) <= _clothes.MAX_BANDS:
+        raise ValueError("clothes: --bands is 1 .. %d" % _clothes.MAX_BANDS)
+    if widen < 0 or drop < 0 or height < 0 or min_size < 0:
+        raise ValueError("clothes: --widen, --drop, --height and --min-size are not negative")
+    bands, batch = int(bands), int(batch)
+    W, H = video.frame_size
+    rows = _load(tracking, formats.read_tracks)
+    tracks = sorted(set(int(r[1]) for r in rows))
+    row_of = dict((t, k) for k, t in enumerate(tracks))
+    table = np.zeros((len(tracks), _clothes.HEAD + _clothes.BINS * bands), np.int64)
+    table[:, 0], table[:, 1], table[:, 2], table[:, 5] = tracks, -1, -1, bands
+    by_frame = {}                            # frame index -> [(track, window)] of the faces that count
+    for fi, T, faces in faces_per_frame(rows, _frame_times(video, rows), W, H, drop_last=False):
+        if T < t_from or (t_until is not None and not T < t_until):
+            continue
+        faces = [(int(t), b) for t, b in faces]
+        for (t, _), win in zip(faces, _clothes.windows_of(faces, W, H, widen, drop, height, min_size, keep_overlapped)):
+            r = table[row_of[t]]
+            r[1], r[2] = (ms(T) if r[1] < 0 else min(r[1], ms(T))), max(r[2], ms(T))
+            if win is None:
+                r[4] += 1
+            else:
+                r[3] += 1
+                by_frame.setdefault(fi, []).append((t, win))
+    if by_frame:
+        ctx = ctx or runtime.default_context()
+        with FrameFeed(ctx, video, by_frame, ahead=ahead, name="pvface-clothes-reader") as feed:
+            jobs, held = [], []              # [(device frame, track, window)] waiting for a call; [[device frame, its windows still waiting]]
+
+            def call(k):
+                part = jobs[:k]
+                del jobs[:k]
+                _clothes.measure(ctx, [j[0] for j in part], [j[2] for j in part], [j[1] for j in part], bands, table, row_of)
+                while k:                     # a frame goes when its last window has been measured
+                    took = min(k, held[0][1])
+                    held[0][1] -= took
+                    k -= took
+                    if not held[0][1]:
+                        feed.release(held.pop(0)[0])
+            for fi, dev in feed:
+                held.append([dev, len(by_frame[fi])])
+                jobs.extend((dev, t, win) for t, win in by_frame[fi])
+                while len(jobs) >= batch:
+                    call(batch)
+            if jobs:
+                call(len(jobs))
+    if hasattr(output, "write"):
+        np.save(output, table)
+    else:
+        with open(output, "wb") as fo:
+            np.save(fo, table)
+    return {"tracks": len(tracks), "faces": int(table[:, 3].sum()), "skipped": int(table[:, 4].sum())}
+
+
+def link(table, output, min_score=0.75, margin=0.05, max_gap=120.0, min_faces=3, min_pixels=20000, labels=None, merged=None):
+    """Which tracks wear the same clothes (CLOTHES.md "Link"), on the host, from a clothes file alone: JSON {"parameters", "links":
+    [{"a", "b", "score"}]} with a < b, sorted.  With `labels` and `merged` the `identifier name` file of `cluster` or `identify` is
+    written again with the clusters merged along the links.  The pair scores are numpy on the host: a film has a few thousand tracks.
+    Returns the links."""
+    from . import clothes as _clothes, render
+    if (labels is None) != (merged is None):
+        raise ValueError("link: --labels and --merged come together")
+    t = _clothes.load(table) if isinstance(table, str) else _clothes.check(np.asarray(table))
+    found = _clothes.links(t, min_score=min_score, margin=margin, max_gap=max_gap, min_faces=min_faces, min_pixels=min_pixels)
+    doc = {"parameters": {"min_score": _clothes.fraction(min_score, "min-score"), "margin": _clothes.fraction(margin, "margin"),
+                          "max_gap_ms": _clothes.ms(max_gap), "min_faces": int(min_faces), "min_pixels": int(min_pixels)},
+           "links": [{"a": a, "b": b, "score": s} for a, b, s in found]}
+    out = json.dumps(doc, indent=1)
+    if str(output) == "-":
+        sys.stdout.write(out + "\n")
+        sys.stdout.flush()
+    else:
+        with open(output, "w") as fo:
+            fo.write(out + "\n")
+    if labels is not None:
+        names = _clothes.merge_labels(_load(labels, render.read_labels), found, t)
+        with open(merged, "w") as fo:
+            for identifier in sorted(names):
+                fo.write("%d %s\n" % (identifier, names[identifier]))
+    return doc["links"]
+
+
 def demo(video, tracking, output, height=400, t_from=0.0, t_until=None, shift=0.0, landmark=None, label=None, matrix="601",
          full_range=False, fps=None, ctx=None, ring_depth=16):
     """Annotated video (pyannote-face.py:317-413) as YUV4MPEG2, to a path or to stdout (`-`).  What is drawn on which frame is planned
@@ -1314,6 +1418,26 @@ def _parser():
     cp.add_argument("--fill", type=float, default=0.5, help="least share of its box, over its frames, a caption fills, 0 .. 1")
     cp.add_argument("--rows", dest="band", default="0,1", help="A,B: only the cell rows whose centre lies in [A, B) of the frame's height")
     cp.add_argument("--tracking", default=None, help="what `track` wrote: the tracks on screen with each caption")
+    cl = sub.add_parser("clothes", help="a colour histogram of the torso windows under the faces of every track, as an int64 [T][6 + 256 bands] .npy file")
+    cl.add_argument("video"); cl.add_argument("tracking"); cl.add_argument("output", help="the .npy path the table is written to")
+    cl.add_argument("--widen", type=float, default=0.5, help="face widths the window reaches beyond the face box on either side")
+    cl.add_argument("--drop", type=float, default=0.25, help="face heights between the face box and the window's top")
+    cl.add_argument("--height", type=float, default=2.0, help="face heights the window is tall")
+    cl.add_argument("--bands", type=int, default=2, help="horizontal bands of the window with a histogram each, 1 .. 4")
+    cl.add_argument("--min-size", type=float, default=0.0, help="smaller faces are skipped, share of the frame's height")
+    cl.add_argument("--keep-overlapped", action="store_true", help="count windows that meet another track's face box too")
+    cl.add_argument("--from", dest="t_from", type=float, default=0.0, help="faces from this time on, seconds")
+    cl.add_argument("--until", dest="t_until", type=float, default=None, help="faces before this, seconds")
+    cl.add_argument("--batch", type=int, default=2048, help="windows per library call")
+    lk = sub.add_parser("link", help="the tracks that wear the same clothes, from a clothes file of `clothes`, as JSON; the video is not opened")
+    lk.add_argument("table", help="the clothes file"); lk.add_argument("output", help="a path, or - for stdout")
+    lk.add_argument("--min-score", type=float, default=0.75, help="least histogram intersection of a link, 0 .. 1")
+    lk.add_argument("--margin", type=float, default=0.05, help="least lead of a track's best candidate over its second best, 0 .. 1")
+    lk.add_argument("--max-gap", type=float, default=120.0, help="largest time between the two tracks, seconds")
+    lk.add_argument("--min-faces", type=int, default=3, help="tracks with fewer counted faces take no part")
+    lk.add_argument("--min-pixels", type=int, default=20000, help="tracks with fewer counted pixels take no part")
+    lk.add_argument("--labels", default=None, help="`identifier name` lines of `cluster` or `identify`: merged along the links into --merged")
+    lk.add_argument("--merged", default=None, help="the label file written with --labels")
     c = sub.add_parser("cluster")
     c.add_argument("embeddings"); c.add_argument("labels")
     c.add_argument("--threshold", type=float, default=0.6)
@@ -1454,7 +1578,7 @@ def main(argv=None):
         if a.video == "-" and a.verb == "faces":
             ap.error("faces reads the video twice, once for the quality of every face and once for the frames of the chosen ones: "
                      "give it a file, not a stream on stdin")
-        if a.video == "-" and a.verb not in ("track", "process", "talk", "tube", "fingerprint", "blend", "motion", "text"):
+        if a.video == "-" and a.verb not in ("track", "process", "talk", "tube", "fingerprint", "blend", "motion", "text", "clothes"):
             ap.error("%s needs the length of the video: give it a file, not a stream on stdin" % a.verb)
         over = {}
         if a.matrix is not None:
@@ -1559,6 +1683,18 @@ def main(argv=None):
                 raise ValueError("caption: --rows A,B with 0 <= A < B <= 1")
             caption(a.rows, a.output, window=a.window, hold=a.hold, gap=a.gap, min_duration=a.min_duration, min_width=a.min_width,
                     max_height=a.max_height, fill=a.fill, band=band, tracking=a.tracking)
+        except ValueError as e:
+            ap.error(str(e))
+    elif a.verb == "clothes":
+        try:
+            res = clothes(video(), a.tracking, a.output, widen=a.widen, drop=a.drop, height=a.height, bands=a.bands, min_size=a.min_size,
+                          keep_overlapped=a.keep_overlapped, t_from=a.t_from, t_until=a.t_until, batch=a.batch, ctx=ctx)
+        except ValueError as e:
+            ap.error(str(e))
+    elif a.verb == "link":
+        try:
+            link(a.table, a.output, min_score=a.min_score, margin=a.margin, max_gap=a.max_gap, min_faces=a.min_faces, min_pixels=a.min_pixels,
+                 labels=a.labels, merged=a.merged)
         except ValueError as e:
             ap.error(str(e))
     elif a.verb == "demo":

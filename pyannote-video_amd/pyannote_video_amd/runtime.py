@@ -1265,6 +1265,22 @@ class Context(object):
                                          int(on), ptr(rows), ptr(counts) if want_counts else None))
         return rows, counts
 
+    def frame_hist(self, frames, windows, group, G, bands=2, out_ptr=None):
+        """the colour histograms of windows of resident frames, of any sizes (pvf_frame_hist; CLOTHES.md): uint32 [G, bands, 256], the
+        pixels of the windows (x0, y0, x1, y1) -- int32 pixels, half-open, clipped to their frame -- of every group, per band.  With
+        out_ptr, a device address that holds as much, the counts stay in HBM and nothing is returned."""
+        n = len(frames)
+        windows = np.ascontiguousarray(windows, np.int32).reshape(-1, 4)
+        group = np.ascontiguousarray(group, np.int32).reshape(-1)
+        if len(windows) != n or len(group) != n:
+            raise ValueError("frame_hist: one window (x0, y0, x1, y1) and one group per frame")
+        G, bands = int(G), int(bands)
+        out = None if out_ptr is not None else np.empty((G, bands, 256) if G >= 1 and 1 <= bands <= 4 and G * bands <= 65536 else (0,), np.uint32)
+        with self._staging():
+            check(self._l.pvf_frame_hist(self._h, ptr(self._handles(frames)) if n else None, ptr(windows) if n else None, ptr(group) if n else None, n,
+                                         G, bands, C.c_void_p(int(out_ptr)) if out_ptr is not None else ptr(out), 1 if out_ptr is not None else 0))
+        return out
+
     # The four agglomerating calls have a `_cooccur` sibling that takes `extent` (float64 [T, 2]: start and end of every track, seconds):
     # the do-not-cooccur constraint (clustering.py:142-143; pvf_cluster_*_cooccur) -- tracks whose extents intersect never share a
     # cluster.  They return (labels, merge log, n_blocked = the co-occurring pairs); `flags` bit 0 is the library's test switch
