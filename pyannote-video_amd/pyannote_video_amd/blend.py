@@ -4,7 +4,7 @@ Nothing here touches the device but `Carry.measure`, which calls runtime.Context
 import numpy as np
 
 from .storyboard import tile_size        # noqa: F401 -- th follows from --width as a storyboard thumbnail's does
-from .talk import ms
+from .talk import half_up, ms
 
 LAGS = (4, 8, 16, 32)                    # PVF_BLEND_LAGS
 ABSENT = 0xFFFFFFFF                      # a sum whose earlier frame does not exist
@@ -12,10 +12,6 @@ MAX_PIXELS = 16384                       # PVF_BLEND_MAX_PIXELS
 HISTORY = 32                             # PVF_BLEND_MAX_HISTORY
 WORDS = 16
 KINDS = ("dissolve", "fade-out", "fade-in", "blank", "camera")       # camera: with `transition --motion` only
-
-
-def half_up(x):
-    return int(np.floor(float(x) + 0.5))
 
 
 def stamp(rows, first, frame_rate):
@@ -38,9 +34,10 @@ class Carry(object):
         self.hist = np.zeros((0, self.tw * self.th), np.uint8)
 
     def measure(self, frames):
+        """-> (rows uint32 [len(frames), 16], the frames the caller may release now: all of them, the planes are what is carried)"""
         rows, luma = self.ctx.frame_blend(frames, self.tw, self.th, hist=self.hist)
         self.hist = np.concatenate([self.hist, luma])[-HISTORY:]
-        return rows
+        return rows, list(frames)
 
 
 def load(path):

@@ -204,19 +204,26 @@ def track(video, shot, output, detect_min_size=0.0, detect_every=0.0, track_min_
     bulk tracker work, the state machine one shot behind, frames released shot by shot."""
     pipe = _pipeline(video, ctx, detect_min_size=detect_min_size, detect_every=detect_every, track_min_overlap_ratio=track_min_overlap_ratio,
                      track_min_confidence=track_min_confidence, track_max_gap=track_max_gap)
-    shots = load_shots(shot) if isinstance(shot, str) else shot
-    state = {"next": 0}
+    shots = _load(shot, load_shots)
     with open(output, 'w') as foutput:
-        def write(tracks):
-            for trk in tracks:
-                for line in formats.track_lines(state["next"], trk):
-                    foutput.write(line)
-                foutput.flush()
-                state["next"] += 1
         tm = {}
-        res = pipe.run_stream(video, shots, extract=False, cluster=False, on_tracks=write, timings=tm)
+        res = pipe.run_stream(video, shots, extract=False, cluster=False, on_tracks=_track_writer(foutput), timings=tm)
         res["timings"] = tm
         return res
+
+
+def _track_writer(foutput):
+    """the on_tracks of `track` and `process`: the finished tracks, numbered from 0 as they come, one line per (track, frame), flushed
+    per track"""
+    import itertools
+    numbers = itertools.count()
+
+    def write(tracks):
+        for trk in tracks:
+            for line in formats.track_lines(next(numbers), trk):
+                foutput.write(line)
+            foutput.flush()
+    return write
 
 
 def _jitter_kw(num_jitters, jitter_seed):
@@ -249,7 +256,6 @@ def extract(video, landmark_model, embedding_model, tracking, landmark_output, e
     state = {"error": None}                  # the writer thread's
     with FrameFeed(ctx, video, want, ahead=ahead, name="pvface-extract-reader") as feed, \
             open(landmark_output, 'wb') as flandmark, open(embedding_output, 'wb') as fembedding:
-        pend_f, pend_b, pend_k = [], [], []
         wq = queue.Queue(maxsize=4)
 
         def writer():
@@ -271,25 +277,14 @@ def extract(video, landmark_model, embedding_model, tracking, landmark_output, e
 
         wth = threading.Thread(target=writer, name="pvface-extract-writer")
         wth.start()
-
-        def flush():
-            if not pend_b:
-                return
-            pts, emb = ctx.landmarks_embed(pend_f, pend_b, **jitter)
-            wq.put(([k[0] for k in pend_k], [k[1] for k in pend_k], pts, emb))
-            feed.release_all(pend_f)
-            del pend_f[:], pend_b[:], pend_k[:]
         try:
-            for fi, dev in feed:
+            for part in feed.batches(batch, lambda fi: len(want[fi][1])):
                 if state["error"] is not None:
                     break
-                T, g = want[fi]
-                for ident, box in g:
-                    pend_f.append(dev); pend_b.append(box); pend_k.append((T, ident))
-                if len(pend_b) >= batch:
-                    flush()
-            if state["error"] is None:
-                flush()
+                jobs = [(dev, box, want[fi][0], ident) for fi, dev in part for ident, box in want[fi][1]]
+                pts, emb = ctx.landmarks_embed([j[0] for j in jobs], [j[1] for j in jobs], **jitter)
+                wq.put(([j[2] for j in jobs], [j[3] for j in jobs], pts, emb))
+                feed.release_all(dev for _, dev in part)
         finally:
             wq.put(None)
             wth.join()
@@ -310,17 +305,10 @@ def process(video, shot, landmark_model, embedding_model, tracking_output, landm
     pipe = _pipeline(video, ctx, landmark_model, embedding_model, detect_min_size=detect_min_size, detect_every=detect_every,
                      track_min_overlap_ratio=track_min_overlap_ratio, track_min_confidence=track_min_confidence, track_max_gap=track_max_gap,
                      threshold=threshold, constraint="cooccur" if do_not_cooccur else None)
-    shots = load_shots(shot) if isinstance(shot, str) else shot
-    state = {"next": 0}
+    shots = _load(shot, load_shots)
     with open(tracking_output, 'w') as foutput:
-        def write(tracks):
-            for trk in tracks:
-                for line in formats.track_lines(state["next"], trk):
-                    foutput.write(line)
-                foutput.flush()
-                state["next"] += 1
         tm = {}
-        res = pipe.run_stream(video, shots, on_tracks=write, cluster=label_output is not None, timings=tm)
+        res = pipe.run_stream(video, shots, on_tracks=_track_writer(foutput), cluster=label_output is not None, timings=tm)
         res["timings"] = tm
     w, h = video.size
     with open(landmark_output, 'wb') as flandmark, open(embedding_output, 'wb') as fembedding:
@@ -357,6 +345,44 @@ def _frame_times(video, rows):
     except TypeError:
         n_frames = int(max([r[0] for r in rows] or [0.0]) * video.frame_rate) + 2
     return [i / video.frame_rate for i in range(n_frames)]
+
+
+def _save_array(output, array):
+    """a verb's table as a .npy file: `output` is a path, or an open binary file"""
+    if hasattr(output, "write"):
+        np.save(output, array)
+    else:
+        with open(output, "wb") as fo:
+            np.save(fo, array)
+
+
+def _write_json(output, doc):
+    """a verb's findings as JSON: `output` is a path, or - for stdout"""
+    text = json.dumps(doc, indent=1) + "\n"
+    if str(output) == "-":
+        sys.stdout.write(text)
+        sys.stdout.flush()
+    else:
+        with open(output, "w") as fo:
+            fo.write(text)
+
+
+def _check_sheet_name(verb, output):
+    if not (str(output) == "-" or str(output).endswith((".ppm", ".npy"))):
+        raise ValueError("%s: the output is a .ppm or .npy path, or - for a PPM on stdout" % verb)
+
+
+def _write_sheet(output, sheet):
+    """a contact sheet, uint8 [H, W, 3]: a binary PPM to a `.ppm` path or, for -, to stdout; the array itself to a `.npy` path"""
+    from .faces import ppm_bytes
+    if str(output).endswith(".npy"):
+        np.save(output, sheet)
+    elif str(output) == "-":
+        sys.stdout.buffer.write(ppm_bytes(sheet))
+        sys.stdout.buffer.flush()
+    else:
+        with open(output, "wb") as fo:
+            fo.write(ppm_bytes(sheet))
 
 
 def cluster(embeddings, output, threshold=0.6, force=False, metric="euclidean", ctx=None, do_not_cooccur=False):
@@ -499,7 +525,7 @@ def shot(video, output, height=50, window=2.0, threshold=1.0, ctx=None):
 def thread(video, shot, output, min_match=20, lookahead=24, ctx=None):
     """Shot threading (scripts/pyannote-structure.py:72-80): reads what `shot` writes, writes a pyannote.core.json Annotation"""
     from .structure import Thread, Segment
-    shots = [Segment(s.start, s.end) for s in (load_shots(shot) if isinstance(shot, str) else shot)]
+    shots = [Segment(s.start, s.end) for s in _load(shot, load_shots)]
     threads = Thread(video, shot=shots, lookahead=lookahead, min_match=min_match, ctx=ctx)()
     with open(output, 'w') as fp:
         json.dump(threads.for_json(), fp)
@@ -525,11 +551,10 @@ def storyboard(video, shot, output, per=1, width=160, columns=None, thread=None,
     """The shots of a film as a contact sheet (STORYBOARD.md): `per` frames of every shot, whole, as thumbnails `width` pixels wide under
     a caption, coloured by thread with `thread` (what `thread` or `scene` wrote).  The frames are read by one seeking FrameFeed and
     reduced on the device `batch` at a time (storyboard.build).  Returns {"width", "height", "shots", "tiles"}."""
-    from . import storyboard as _board, faces as _faces, runtime
+    from . import storyboard as _board, runtime
     from ._core import Annotation
-    if not (str(output) == "-" or str(output).endswith((".ppm", ".npy"))):
-        raise ValueError("storyboard: the output is a .ppm or .npy path, or - for a PPM on stdout")
-    shots = load_shots(shot) if isinstance(shot, str) else list(shot)
+    _check_sheet_name("storyboard", output)
+    shots = list(_load(shot, load_shots))
     annotation = None
     if thread is not None:
         if isinstance(thread, str):
@@ -543,14 +568,7 @@ def storyboard(video, shot, output, per=1, width=160, columns=None, thread=None,
     if index:
         with open(index, "w") as fx:
             fx.write("".join(lines))
-    if str(output) == "-":
-        sys.stdout.buffer.write(_faces.ppm_bytes(sheet))
-        sys.stdout.buffer.flush()
-    elif str(output).endswith(".npy"):
-        np.save(output, sheet)
-    else:
-        with open(output, "wb") as fo:
-            fo.write(_faces.ppm_bytes(sheet))
+    _write_sheet(output, sheet)
     return res
 
 
@@ -560,41 +578,19 @@ def fingerprint(video, output, t_from=0.0, t_until=None, batch=64, ctx=None, ahe
     (32 bytes a frame come back) and releases them.  Writes uint64 [n][4] -- H, V, SY | RANGE << 32, ms(T) | frame index << 32 -- as
     a .npy file (`output` may be an open binary file).  Returns {"frames", "first"}."""
     from . import repeat as _repeat, runtime
-    from .feed import FrameFeed
+    from .feed import FrameFeed, frame_range
     if int(batch) < 1:
         raise ValueError("fingerprint: a batch holds at least one frame")
-    rate = float(video.frame_rate)
-    first = 0
-    while first / rate < t_from:
-        first += 1
-    end = None
-    if t_until is not None:
-        end = first
-        while end / rate < t_until:
-            end += 1
-    try:
-        end = len(video) if end is None else min(end, len(video))
-    except TypeError:                        # a stream: as far as it goes
-        pass
+    first, end = frame_range(video, t_from, t_until)
     ctx = ctx or runtime.default_context()
-    parts, pend = [], []
+    parts = []
     with FrameFeed(ctx, video, _repeat.EveryFrame(first, end), ahead=max(ahead, 2 * int(batch)), name="pvface-fingerprint-reader") as feed:
-        def flush():
-            parts.append(ctx.frame_prints(pend))
-            feed.release_all(pend)
-            del pend[:]
-        for _, dev in feed:
-            pend.append(dev)
-            if len(pend) >= batch:
-                flush()
-        if pend:
-            flush()
-    prints = _repeat.stamp(np.concatenate(parts) if parts else np.zeros((0, 4), np.uint64), first, rate)
-    if hasattr(output, "write"):
-        np.save(output, prints)
-    else:
-        with open(output, "wb") as fo:
-            np.save(fo, prints)
+        for part in feed.batches(batch):
+            frames = [dev for _, dev in part]
+            parts.append(ctx.frame_prints(frames))
+            feed.release_all(frames)
+    prints = _repeat.stamp(np.concatenate(parts) if parts else np.zeros((0, 4), np.uint64), first, video.frame_rate)
+    _save_array(output, prints)
     return {"frames": int(len(prints)), "first": first}
 
 
@@ -610,13 +606,7 @@ def repeat(output, prints, max_bits=10, flat=16, min_duration=2.0, max_gap=0.5, 
     files = [(str(p), _repeat.load(p)) for p in prints]
     found = _repeat.compare(ctx or runtime.default_context(), files, max_bits=max_bits, flat=flat, min_duration=min_duration, max_gap=max_gap,
                             min_separation=min_separation)
-    text = json.dumps(found, indent=1)
-    if str(output) == "-":
-        sys.stdout.write(text + "\n")
-        sys.stdout.flush()
-    else:
-        with open(output, "w") as fo:
-            fo.write(text + "\n")
+    _write_json(output, found)
     return found
 
 
@@ -626,46 +616,24 @@ def blend(video, output, width=64, t_from=0.0, t_until=None, batch=64, ctx=None,
     file does not depend on `batch`.  The thumbnail is `width` pixels wide and keeps the frame's aspect.  Writes uint32 [n][16], stamped
     with ms(T) and the frame index, as a .npy file (`output` may be an open binary file).  Returns {"frames", "first", "tw", "th"}."""
     from . import blend as _blend, repeat as _repeat, runtime
-    from .feed import FrameFeed
+    from .feed import FrameFeed, frame_range
     if int(batch) < 1:
         raise ValueError("blend: a batch holds at least one frame")
     if int(width) < 1:
         raise ValueError("blend: --width is at least 1")
-    rate = float(video.frame_rate)
     w, h = video.frame_size
     tw, th = _blend.tile_size(width, w, h)
-    first = 0
-    while first / rate < t_from:
-        first += 1
-    end = None
-    if t_until is not None:
-        end = first
-        while end / rate < t_until:
-            end += 1
-    try:
-        end = len(video) if end is None else min(end, len(video))
-    except TypeError:                        # a stream: as far as it goes
-        pass
+    first, end = frame_range(video, t_from, t_until)
     ctx = ctx or runtime.default_context()
     carry = _blend.Carry(ctx, tw, th)
-    parts, pend = [], []
+    parts = []
     with FrameFeed(ctx, video, _repeat.EveryFrame(first, end), ahead=max(ahead, 2 * int(batch)), name="pvface-blend-reader") as feed:
-        def flush():
-            parts.append(carry.measure(pend))
-            feed.release_all(pend)
-            del pend[:]
-        for _, dev in feed:
-            pend.append(dev)
-            if len(pend) >= batch:
-                flush()
-        if pend:
-            flush()
-    rows = _blend.stamp(np.concatenate(parts) if parts else np.zeros((0, _blend.WORDS), np.uint32), first, rate)
-    if hasattr(output, "write"):
-        np.save(output, rows)
-    else:
-        with open(output, "wb") as fo:
-            np.save(fo, rows)
+        for part in feed.batches(batch):
+            rows, done = carry.measure([dev for _, dev in part])
+            parts.append(rows)
+            feed.release_all(done)
+    rows = _blend.stamp(np.concatenate(parts) if parts else np.zeros((0, _blend.WORDS), np.uint32), first, video.frame_rate)
+    _save_array(output, rows)
     return {"frames": int(len(rows)), "first": first, "tw": tw, "th": th}
 
 
@@ -685,15 +653,9 @@ def transition(rows, output, move=4.0, linear=0.25, flat=2.0, min_duration=0.12,
         more["moving"] = _motion.moving_frames(_motion.load(motion, "transition") if isinstance(motion, str) else np.ascontiguousarray(motion))
     found, cuts = _blend.analyse(table, move=move, linear=linear, flat=flat, min_duration=min_duration, **more)
     listed = _blend.report(table, found)
-    text = json.dumps(listed, indent=1)
-    if str(output) == "-":
-        sys.stdout.write(text + "\n")
-        sys.stdout.flush()
-    else:
-        with open(output, "w") as fo:
-            fo.write(text + "\n")
+    _write_json(output, listed)
     if shots is not None:
-        before = [(s.start, s.end) for s in (load_shots(shots) if isinstance(shots, str) else shots)]
+        before = [(s.start, s.end) for s in _load(shots, load_shots)]
         pieces = _blend.refine(before, [int(table[c, 12]) / 1000.0 for c in cuts])
         with open(refined, "w") as fp:
             json.dump({"pyannote": "Timeline", "content": [{"start": a, "end": b} for a, b in pieces]}, fp)
@@ -708,51 +670,24 @@ def motion(video, output, width=96, t_from=0.0, t_until=None, batch=256, ctx=Non
     depend on `batch`.  The first frame of the range has no frame before it and gets a row without valid pixels.  Writes int64 [n][10],
     stamped with ms(T) | index << 32, as a .npy file (`output` may be an open binary file).  Returns {"frames", "first", "tw", "th"}."""
     from . import motion as _motion, repeat as _repeat, runtime
-    from .feed import FrameFeed
+    from .feed import FrameFeed, frame_range
     if int(batch) < 1:
         raise ValueError("motion: a batch holds at least one frame")
     if int(width) < 1:
         raise ValueError("motion: --width is at least 1")
-    rate = float(video.frame_rate)
     w, h = video.frame_size
     tw, th = _motion.tile_size(width, w, h)
-    first = 0
-    while first / rate < t_from:
-        first += 1
-    end = None
-    if t_until is not None:
-        end = first
-        while end / rate < t_until:
-            end += 1
-    try:
-        end = len(video) if end is None else min(end, len(video))
-    except TypeError:                        # a stream: as far as it goes
-        pass
+    first, end = frame_range(video, t_from, t_until)
     ctx = ctx or runtime.default_context()
-    pairs = _motion.Pairs(ctx, tw, th)
-    parts, pend = [], []
+    carry = _motion.Pairs(ctx, tw, th)
+    parts = []
     with FrameFeed(ctx, video, _repeat.EveryFrame(first, end), ahead=max(ahead, 2 * int(batch)), name="pvface-motion-reader") as feed:
-        def flush():
-            rows, done = pairs.measure(pend)
+        for part in feed.batches(batch):
+            rows, done = carry.measure([dev for _, dev in part])
             parts.append(rows)
-            feed.release_all(pend[:-1])          # the last one is the next call's first frame
-            if done is not None:
-                feed.release(done)
-            del pend[:]
-        for _, dev in feed:
-            pend.append(dev)
-            if len(pend) >= batch:
-                flush()
-        if pend:
-            flush()
-        if pairs.held is not None:
-            feed.release(pairs.held)
-    rows = _motion.stamp(np.concatenate(parts) if parts else np.zeros((0, _motion.WORDS), np.int64), first, rate)
-    if hasattr(output, "write"):
-        np.save(output, rows)
-    else:
-        with open(output, "wb") as fo:
-            np.save(fo, rows)
+            feed.release_all(done)
+    rows = _motion.stamp(np.concatenate(parts) if parts else np.zeros((0, _motion.WORDS), np.int64), first, video.frame_rate)
+    _save_array(output, rows)
     return {"frames": int(len(rows)), "first": first, "tw": tw, "th": th}
 
 
@@ -763,17 +698,11 @@ def camera(rows, output, pan=5.0, zoom=3.0, window=0.5, min_inliers=50, min_dura
     from . import motion as _motion
     table = _motion.load(rows) if isinstance(rows, str) else np.ascontiguousarray(rows)
     if shots is not None:
-        shots = [(s.start, s.end) for s in (load_shots(shots) if isinstance(shots, str) else shots)]
+        shots = [(s.start, s.end) for s in _load(shots, load_shots)]
     found = _motion.analyse(table, pan=pan, zoom=zoom, window=window, min_inliers=min_inliers, min_duration=min_duration, max_gap=max_gap,
                             shots=shots)
     listed = _motion.report(table, found)
-    text = json.dumps(listed, indent=1)
-    if str(output) == "-":
-        sys.stdout.write(text + "\n")
-        sys.stdout.flush()
-    else:
-        with open(output, "w") as fo:
-            fo.write(text + "\n")
+    _write_json(output, listed)
     return listed
 
 
@@ -784,53 +713,26 @@ def text(video, output, step=0.0, edge=48, still=8, on=24, t_from=0.0, t_until=N
     (text.Carry), so the file does not depend on `batch`.  Writes uint32 [n][8 + ch wpr], stamped with ms(T) and the frame index, as a
     .npy file (`output` may be an open binary file).  Returns {"frames", "first", "every"}."""
     from . import text as _text, runtime
-    from .feed import FrameFeed
+    from .feed import EveryKth, FrameFeed, frame_range
     if not 1 <= int(batch) <= _text.MAX_FRAMES:
         raise ValueError("text: a batch holds 1 .. %d frames" % _text.MAX_FRAMES)
     if step < 0:
         raise ValueError("text: --step is not negative")
-    rate = float(video.frame_rate)
     w, h = video.frame_size
     if not (1 <= w <= _text.MAX_SIDE and 1 <= h <= _text.MAX_SIDE):
         raise ValueError("text: frames of %d x %d; sides of at most %d are measured" % (w, h, _text.MAX_SIDE))
-    k = _text.every(step, rate)
-    first = 0
-    while first / rate < t_from:
-        first += 1
-    end = None
-    if t_until is not None:
-        end = first
-        while end / rate < t_until:
-            end += 1
-    try:
-        end = len(video) if end is None else min(end, len(video))
-    except TypeError:                        # a stream: as far as it goes
-        pass
+    k = _text.every(step, video.frame_rate)
+    first, end = frame_range(video, t_from, t_until)
     ctx = ctx or runtime.default_context()
     carry = _text.Carry(ctx, edge=edge, still=still, on=on)
-    parts, pend = [], []
-    with FrameFeed(ctx, video, _text.EveryKth(first, end, k), ahead=max(ahead, 2 * int(batch)), name="pvface-text-reader") as feed:
-        def flush():
-            rows, done = carry.measure(pend)
+    parts = []
+    with FrameFeed(ctx, video, EveryKth(first, end, k), ahead=max(ahead, 2 * int(batch)), name="pvface-text-reader") as feed:
+        for part in feed.batches(batch):
+            rows, done = carry.measure([dev for _, dev in part])
             parts.append(rows)
-            feed.release_all(pend[:-1])          # the last one is the next call's prev
-            if done is not None:
-                feed.release(done)
-            del pend[:]
-        for _, dev in feed:
-            pend.append(dev)
-            if len(pend) >= batch:
-                flush()
-        if pend:
-            flush()
-        if carry.held is not None:
-            feed.release(carry.held)
-    rows = _text.stamp(np.concatenate(parts) if parts else np.zeros((0, _text.row_words(w, h)), np.uint32), first, rate, k)
-    if hasattr(output, "write"):
-        np.save(output, rows)
-    else:
-        with open(output, "wb") as fo:
-            np.save(fo, rows)
+            feed.release_all(done)
+    rows = _text.stamp(np.concatenate(parts) if parts else np.zeros((0, _text.row_words(w, h)), np.uint32), first, video.frame_rate, k)
+    _save_array(output, rows)
     return {"frames": int(len(rows)), "first": first, "every": k}
 
 
@@ -840,20 +742,11 @@ def caption(rows, output, window=1.0, hold=0.5, gap=1, min_duration=1.0, min_wid
     whether one is `alone`.  The video is not opened.  Returns the list."""
     from . import text as _text
     table = _text.load(rows) if isinstance(rows, str) else _text.check(np.asarray(rows))
-    tracks = None
-    if tracking is not None:
-        from . import formats
-        tracks = formats.read_tracks(tracking) if isinstance(tracking, str) else tracking
+    tracks = _load(tracking, formats.read_tracks)
     found = _text.analyse(table, window=window, hold=hold, gap=gap, min_duration=min_duration, min_width=min_width, max_height=max_height,
                           fill=fill, band=band)
     listed = _text.report(table, found, tracks)
-    out = json.dumps(listed, indent=1)
-    if str(output) == "-":
-        sys.stdout.write(out + "\n")
-        sys.stdout.flush()
-    else:
-        with open(output, "w") as fo:
-            fo.write(out + "\n")
+    _write_json(output, listed)
     return listed
 
 
@@ -917,11 +810,7 @@ def clothes(video, tracking, output, widen=0.5, drop=0.25, height=2.0, bands=2, 
                     call(batch)
             if jobs:
                 call(len(jobs))
-    if hasattr(output, "write"):
-        np.save(output, table)
-    else:
-        with open(output, "wb") as fo:
-            np.save(fo, table)
+    _save_array(output, table)
     return {"tracks": len(tracks), "faces": int(table[:, 3].sum()), "skipped": int(table[:, 4].sum())}
 
 
@@ -938,13 +827,7 @@ def link(table, output, min_score=0.75, margin=0.05, max_gap=120.0, min_faces=3,
     doc = {"parameters": {"min_score": _clothes.fraction(min_score, "min-score"), "margin": _clothes.fraction(margin, "margin"),
                           "max_gap_ms": _clothes.ms(max_gap), "min_faces": int(min_faces), "min_pixels": int(min_pixels)},
            "links": [{"a": a, "b": b, "score": s} for a, b, s in found]}
-    out = json.dumps(doc, indent=1)
-    if str(output) == "-":
-        sys.stdout.write(out + "\n")
-        sys.stdout.flush()
-    else:
-        with open(output, "w") as fo:
-            fo.write(out + "\n")
+    _write_json(output, doc)
     if labels is not None:
         names = _clothes.merge_labels(_load(labels, render.read_labels), found, t)
         with open(merged, "w") as fo:
@@ -1064,8 +947,7 @@ def faces(video, tracking, landmarks, output, per=4, tile=150, columns=None, lab
     from . import faces as _faces, render, runtime
     from .feed import FrameFeed
     ctx = ctx or runtime.default_context()
-    if not (str(output) == "-" or str(output).endswith((".ppm", ".npy"))):
-        raise ValueError("faces: the output is a .ppm or .npy path, or - for a PPM on stdout")
+    _check_sheet_name("faces", output)
     if not _faces.MIN_TILE <= int(tile) <= _faces.MAX_TILE:
         raise ValueError("faces: --tile is %d .. %d" % (_faces.MIN_TILE, _faces.MAX_TILE))
     if int(per) < 1:
@@ -1080,19 +962,11 @@ def faces(video, tracking, landmarks, output, per=4, tile=150, columns=None, lab
 
     # ---- pass 1: the quality of every face
     with FrameFeed(ctx, video, by_frame, ahead=ahead, name="pvface-faces-reader") as feed:
-        pend_f, pend_i = [], []
-
-        def flush():
-            if pend_i:
-                sums[pend_i] = ctx.face_quality(pend_f, np.stack([all_faces[i][4] for i in pend_i]))
-            feed.release_all(pend_f)
-            del pend_f[:], pend_i[:]
-        for fi, dev in feed:
-            for i in by_frame[fi]:
-                pend_f.append(dev); pend_i.append(i)
-            if len(pend_i) >= batch:
-                flush()
-        flush()
+        for part in feed.batches(batch, lambda fi: len(by_frame[fi])):
+            jobs = [(dev, i) for fi, dev in part for i in by_frame[fi]]
+            idx = [i for _, i in jobs]
+            sums[idx] = ctx.face_quality([dev for dev, _ in jobs], np.stack([all_faces[i][4] for i in idx]))
+            feed.release_all(dev for _, dev in part)
 
     # ---- the choice
     sym = [_faces.symmetry(f[4]) for f in all_faces]
@@ -1125,14 +999,7 @@ def faces(video, tracking, landmarks, output, per=4, tile=150, columns=None, lab
         dev = dict(feed)
         sheet = ctx.face_sheet([dev[all_faces[i][2]] for i in flat], np.stack([all_faces[i][4] for i in flat]),
                                [xy for c in corners for xy in c], int(tile), W, H, _faces.BACKGROUND, prims)
-    if str(output) == "-":
-        sys.stdout.buffer.write(_faces.ppm_bytes(sheet))
-        sys.stdout.buffer.flush()
-    elif str(output).endswith(".npy"):
-        np.save(output, sheet)
-    else:
-        with open(output, "wb") as fo:
-            fo.write(_faces.ppm_bytes(sheet))
+    _write_sheet(output, sheet)
     return {"width": W, "height": H, "groups": [g[0] for g in groups], "faces": len(all_faces), "shown": len(flat)}
 
 
@@ -1160,11 +1027,10 @@ def talk(video, tracking, landmarks, output, window=0.4, on=3.0, off=1.5, min_du
     out = np.full((len(all_faces), 8), -1, np.int32)
 
     with FrameFeed(ctx, video, by_frame, ahead=ahead, name="pvface-talk-reader") as feed:
-        carry, pend = [], []                 # [(frame index, device frame)]; carry: the last frame of the batch before
-
-        def flush():
+        carry = []                           # [(frame index, device frame)]: the last frame of the batch before
+        for part in feed.batches(batch, lambda fi: len(by_frame[fi])):
             frames, idx = [], []
-            for fi, dev in carry + pend:
+            for fi, dev in carry + part:
                 for i in by_frame[fi]:
                     frames.append(dev); idx.append(i)
             lead = sum(len(by_frame[fi]) for fi, _ in carry)
@@ -1172,15 +1038,8 @@ def talk(video, tracking, landmarks, output, window=0.4, on=3.0, off=1.5, min_du
             p = [-1 if k < lead else local.get(prev[i], -1) for k, i in enumerate(idx)]
             got = ctx.face_motion(frames, np.stack([all_faces[i][4] for i in idx]), p)
             out[idx[lead:]] = got[lead:]
-            feed.release_all(dev for _, dev in carry + pend[:-1])
-            carry[:] = pend[-1:]
-            del pend[:]
-        for item in feed:
-            pend.append(item)
-            if sum(len(by_frame[fi]) for fi, _ in pend) >= batch:
-                flush()
-        if pend:
-            flush()
+            feed.release_all(dev for _, dev in carry + part[:-1])
+            carry = part[-1:]
 
     linked = [p >= 0 for p in prev]
     per, segs = _talk.analyse([(f[0], f[1], f[4]) for f in all_faces], out, linked, window, on, off, min_duration, max_pause, max_dark)
@@ -1252,26 +1111,15 @@ def tube(video, tracking, landmarks, output, size=224, region="face", scale=None
 
     try:
         with FrameFeed(ctx, video, by_frame, ahead=ahead, name="pvface-tube-reader") as feed:
-            pend = []                        # [(frame index, device frame)]
-
-            def flush():
-                frames, jobs = [], []
-                for fi, dev in pend:
-                    for job in by_frame[fi]:
-                        frames.append(dev); jobs.append(job)
+            for part in feed.batches(batch, lambda fi: len(by_frame[fi])):
+                jobs = [(dev, job) for fi, dev in part for job in by_frame[fi]]
                 for k0 in range(0, len(jobs), int(batch)):
-                    part = jobs[k0:k0 + int(batch)]
-                    got = (ctx.frame_warps if align else ctx.frame_crops)(frames[k0:k0 + int(batch)], [j[2] for j in part], size, "rgb" if fmt == "npy" else "yuv420", matrix, full_range)
-                    for (ti, _, _), picture in zip(part, got):
+                    call = jobs[k0:k0 + int(batch)]
+                    got = (ctx.frame_warps if align else ctx.frame_crops)([dev for dev, _ in call], [job[2] for _, job in call], size,
+                                                                          "rgb" if fmt == "npy" else "yuv420", matrix, full_range)
+                    for (_, (ti, _, _)), picture in zip(call, got):
                         write(ti, picture)
-                feed.release_all(dev for _, dev in pend)
-                del pend[:]
-            for item in feed:
-                pend.append(item)
-                if sum(len(by_frame[fi]) for fi, _ in pend) >= batch:
-                    flush()
-            if pend:
-                flush()
+                feed.release_all(dev for _, dev in part)
     finally:
         for wr in writers.values():
             wr.close()
@@ -1563,6 +1411,13 @@ def parse_args(argv=None):
     return _parser().parse_args(argv)
 
 
+# the refusals of a verb that are the user's to mend, and so become usage errors (exit status 2) instead of tracebacks; a verb that is
+# not listed lets every exception through
+_REFUSALS = dict.fromkeys(("cast", "search", "storyboard", "repeat", "blend", "transition", "motion", "camera", "text", "caption", "clothes",
+                           "link", "faces"), (ValueError,))
+_REFUSALS.update(talk=(KeyError, ValueError), tube=(KeyError, ValueError))      # KeyError: a track or name the files do not hold
+
+
 def main(argv=None):
     ap = _parser()
     a = ap.parse_args(argv)
@@ -1572,6 +1427,30 @@ def main(argv=None):
         from .runtime import Context
         ctx = Context(device=a.device)
     t_begin = time.perf_counter()
+    refused = _REFUSALS.get(a.verb, ())
+    try:
+        res = _run(ap, a, ctx)
+    except refused as e:
+        ap.error(str(e.args[0]) if KeyError in refused and e.args else str(e))           # (a KeyError's own text wears quotes)
+    if a.metrics:
+        from . import runtime
+        m = {"verb": a.verb, "seconds": round(time.perf_counter() - t_begin, 4)}
+        if isinstance(res, dict):
+            m.update(frames=res.get("frames"), tracks=len(res.get("tracks", ())), faces=int(len(res["face_T"])) if "face_T" in res else None,
+                     clusters=len(set(res["labels"].values())) if res.get("labels") else None, peak_frames_resident=res.get("peak_frames_resident"),
+                     stage_seconds={k: round(v, 4) for k, v in res.get("timings", {}).items()})
+        try:
+            free, total = (ctx or runtime.default_context()).mem_info()
+            m["device_memory_in_use_bytes"] = total - free
+        except Exception:          # noqa: BLE001 -- the figure is optional
+            pass
+        with open(a.metrics, "w") as f:
+            json.dump(m, f, indent=1)
+    return 0
+
+
+def _run(ap, a, ctx):
+    """the verb of the parsed arguments `a`: its argument checks, which refuse through ap.error, and its call -> what the verb returned"""
     res = None
 
     def video():
@@ -1609,16 +1488,10 @@ def main(argv=None):
     elif a.verb == "enroll-track":
         enroll_track(a.embeddings, a.track, a.name, a.gallery, append=a.append)
     elif a.verb == "cast":
-        try:
-            cast(a.output, a.embeddings, k=a.k, max_distance=a.max_distance, threshold=a.threshold, by=a.by, labels=a.labels, graph=a.graph, ctx=ctx)
-        except ValueError as e:
-            ap.error(str(e))
+        cast(a.output, a.embeddings, k=a.k, max_distance=a.max_distance, threshold=a.threshold, by=a.by, labels=a.labels, graph=a.graph, ctx=ctx)
     elif a.verb == "search":
-        try:
-            search(a.output, a.embeddings, k=a.k, max_distance=a.max_distance, rows=a.rows, include_self=a.include_self, gallery=a.gallery,
-                   name=a.name, source=a.source, track=a.track, ctx=ctx)
-        except ValueError as e:
-            ap.error(str(e))
+        search(a.output, a.embeddings, k=a.k, max_distance=a.max_distance, rows=a.rows, include_self=a.include_self, gallery=a.gallery,
+               name=a.name, source=a.source, track=a.track, ctx=ctx)
     elif a.verb == "shot":
         shot(video(), a.output, height=a.height, window=a.window, threshold=a.threshold, ctx=ctx)
     elif a.verb == "thread":
@@ -1628,11 +1501,8 @@ def main(argv=None):
     elif a.verb == "storyboard":
         if a.width < 1 or a.width > 1024 or a.batch < 1 or (a.columns is not None and a.columns < 1):
             ap.error("--width is 1 .. 1024, --batch and --columns at least 1")
-        try:
-            res = storyboard(video(), a.shot, a.output, per=a.per, width=a.width, columns=a.columns, thread=a.thread, by=a.by, t_from=a.t_from,
-                             t_until=a.t_until, index=a.index, batch=a.batch, ctx=ctx)
-        except ValueError as e:
-            ap.error(str(e))
+        res = storyboard(video(), a.shot, a.output, per=a.per, width=a.width, columns=a.columns, thread=a.thread, by=a.by, t_from=a.t_from,
+                         t_until=a.t_until, index=a.index, batch=a.batch, ctx=ctx)
     elif a.verb == "fingerprint":
         if a.batch < 1:
             ap.error("--batch is at least 1")
@@ -1640,63 +1510,36 @@ def main(argv=None):
     elif a.verb == "repeat":
         if not 0 <= a.max_bits <= 128:
             ap.error("--max-bits is 0 .. 128")
-        try:
-            repeat(a.output, a.prints, max_bits=a.max_bits, flat=a.flat, min_duration=a.min_duration, max_gap=a.max_gap,
-                   min_separation=a.min_separation, ctx=ctx)
-        except ValueError as e:
-            ap.error(str(e))
+        repeat(a.output, a.prints, max_bits=a.max_bits, flat=a.flat, min_duration=a.min_duration, max_gap=a.max_gap,
+               min_separation=a.min_separation, ctx=ctx)
     elif a.verb == "blend":
         if a.batch < 1 or a.width < 1:
             ap.error("--batch and --width are at least 1")
-        try:
-            res = blend(video(), a.output, width=a.width, t_from=a.t_from, t_until=a.t_until, batch=a.batch, ctx=ctx)
-        except ValueError as e:
-            ap.error(str(e))
+        res = blend(video(), a.output, width=a.width, t_from=a.t_from, t_until=a.t_until, batch=a.batch, ctx=ctx)
     elif a.verb == "transition":
-        try:
-            transition(a.rows, a.output, move=a.move, linear=a.linear, flat=a.flat, min_duration=a.min_duration, shots=a.shots, refined=a.refined,
-                       motion=a.motion)
-        except ValueError as e:
-            ap.error(str(e))
+        transition(a.rows, a.output, move=a.move, linear=a.linear, flat=a.flat, min_duration=a.min_duration, shots=a.shots, refined=a.refined,
+                   motion=a.motion)
     elif a.verb == "motion":
         if a.batch < 1 or a.width < 1:
             ap.error("--batch and --width are at least 1")
-        try:
-            res = motion(video(), a.output, width=a.width, t_from=a.t_from, t_until=a.t_until, batch=a.batch, ctx=ctx)
-        except ValueError as e:
-            ap.error(str(e))
+        res = motion(video(), a.output, width=a.width, t_from=a.t_from, t_until=a.t_until, batch=a.batch, ctx=ctx)
     elif a.verb == "camera":
-        try:
-            camera(a.rows, a.output, pan=a.pan, zoom=a.zoom, window=a.window, min_inliers=a.min_inliers, min_duration=a.min_duration,
-                   max_gap=a.max_gap, shots=a.shots)
-        except ValueError as e:
-            ap.error(str(e))
+        camera(a.rows, a.output, pan=a.pan, zoom=a.zoom, window=a.window, min_inliers=a.min_inliers, min_duration=a.min_duration,
+               max_gap=a.max_gap, shots=a.shots)
     elif a.verb == "text":
-        try:
-            res = text(video(), a.output, step=a.step, edge=a.edge, still=a.still, on=a.on, t_from=a.t_from, t_until=a.t_until, batch=a.batch, ctx=ctx)
-        except ValueError as e:
-            ap.error(str(e))
+        res = text(video(), a.output, step=a.step, edge=a.edge, still=a.still, on=a.on, t_from=a.t_from, t_until=a.t_until, batch=a.batch, ctx=ctx)
     elif a.verb == "caption":
-        try:
-            band = tuple(float(v) for v in a.band.split(","))
-            if len(band) != 2:
-                raise ValueError("caption: --rows A,B with 0 <= A < B <= 1")
-            caption(a.rows, a.output, window=a.window, hold=a.hold, gap=a.gap, min_duration=a.min_duration, min_width=a.min_width,
-                    max_height=a.max_height, fill=a.fill, band=band, tracking=a.tracking)
-        except ValueError as e:
-            ap.error(str(e))
+        band = tuple(float(v) for v in a.band.split(","))
+        if len(band) != 2:
+            raise ValueError("caption: --rows A,B with 0 <= A < B <= 1")
+        caption(a.rows, a.output, window=a.window, hold=a.hold, gap=a.gap, min_duration=a.min_duration, min_width=a.min_width,
+                max_height=a.max_height, fill=a.fill, band=band, tracking=a.tracking)
     elif a.verb == "clothes":
-        try:
-            res = clothes(video(), a.tracking, a.output, widen=a.widen, drop=a.drop, height=a.height, bands=a.bands, min_size=a.min_size,
-                          keep_overlapped=a.keep_overlapped, t_from=a.t_from, t_until=a.t_until, batch=a.batch, ctx=ctx)
-        except ValueError as e:
-            ap.error(str(e))
+        res = clothes(video(), a.tracking, a.output, widen=a.widen, drop=a.drop, height=a.height, bands=a.bands, min_size=a.min_size,
+                      keep_overlapped=a.keep_overlapped, t_from=a.t_from, t_until=a.t_until, batch=a.batch, ctx=ctx)
     elif a.verb == "link":
-        try:
-            link(a.table, a.output, min_score=a.min_score, margin=a.margin, max_gap=a.max_gap, min_faces=a.min_faces, min_pixels=a.min_pixels,
-                 labels=a.labels, merged=a.merged)
-        except ValueError as e:
-            ap.error(str(e))
+        link(a.table, a.output, min_score=a.min_score, margin=a.margin, max_gap=a.max_gap, min_faces=a.min_faces, min_pixels=a.min_pixels,
+             labels=a.labels, merged=a.merged)
     elif a.verb == "demo":
         v = video()
         res = demo(v, a.tracking, a.output, height=a.height, t_from=a.t_from, t_until=a.t_until, shift=a.shift, landmark=a.landmark,
@@ -1711,49 +1554,26 @@ def main(argv=None):
                      keep=a.keep, pad=a.pad, cells=a.cells, shape=a.shape, mode=a.mode, colour=a.colour, draw=a.draw, fps=a.fps, ctx=ctx,
                      **colours(v, a.matrix, a.range))
     elif a.verb == "faces":
-        try:
-            res = faces(video(), a.tracking, a.landmarks, a.output, per=a.per, tile=a.tile, columns=a.columns, label=a.label, only=a.only,
-                        spread=a.spread, min_size=a.min_size, max_dark=a.max_dark, max_bright=a.max_bright, t_from=a.t_from, t_until=a.t_until,
-                        index=a.index, quality=a.quality, ctx=ctx)
-        except ValueError as e:
-            ap.error(str(e))
+        res = faces(video(), a.tracking, a.landmarks, a.output, per=a.per, tile=a.tile, columns=a.columns, label=a.label, only=a.only,
+                    spread=a.spread, min_size=a.min_size, max_dark=a.max_dark, max_bright=a.max_bright, t_from=a.t_from, t_until=a.t_until,
+                    index=a.index, quality=a.quality, ctx=ctx)
     elif a.verb == "talk":
-        try:
-            res = talk(video(), a.tracking, a.landmarks, a.output, window=a.window, on=a.on, off=a.off, min_duration=a.min_duration,
-                       max_pause=a.max_pause, max_dark=a.max_dark, t_from=a.t_from, t_until=a.t_until, label=a.label, segments=a.segments, ctx=ctx)
-        except (KeyError, ValueError) as e:
-            ap.error(str(e.args[0]) if e.args else str(e))
+        res = talk(video(), a.tracking, a.landmarks, a.output, window=a.window, on=a.on, off=a.off, min_duration=a.min_duration,
+                   max_pause=a.max_pause, max_dark=a.max_dark, t_from=a.t_from, t_until=a.t_until, label=a.label, segments=a.segments, ctx=ctx)
     elif a.verb == "tube":
         if len(a.rest) > 2:
             ap.error("tube takes <video> <tracking> [<landmarks>] <output-directory>")
-        try:
-            v = video()
-            res = tube(v, a.tracking, a.rest[0] if len(a.rest) == 2 else None, a.rest[-1], size=a.size, region=a.region, scale=a.scale,
-                       smooth=a.smooth, label=a.label, only=a.only, segments=a.segments, min_length=a.min_length, t_from=a.t_from,
-                       t_until=a.t_until, fmt=a.fmt, index=a.index, fps=a.fps, ctx=ctx, align=a.align,
-                       **colours(v, a.out_matrix or a.matrix, a.out_range or a.range))
-        except (KeyError, ValueError) as e:
-            ap.error(str(e.args[0]) if e.args else str(e))
+        v = video()
+        res = tube(v, a.tracking, a.rest[0] if len(a.rest) == 2 else None, a.rest[-1], size=a.size, region=a.region, scale=a.scale,
+                   smooth=a.smooth, label=a.label, only=a.only, segments=a.segments, min_length=a.min_length, t_from=a.t_from,
+                   t_until=a.t_until, fmt=a.fmt, index=a.index, fps=a.fps, ctx=ctx, align=a.align,
+                   **colours(v, a.out_matrix or a.matrix, a.out_range or a.range))
     elif a.verb == "extract":
         extract(video(), a.landmark_model, a.embedding_model, a.tracking, a.landmarks, a.embeddings, ctx=ctx, num_jitters=a.jitters,
                 jitter_seed=a.jitter_seed)
     else:
         cluster(a.embeddings, a.labels, threshold=a.threshold, force=a.force, metric=a.metric, ctx=ctx, do_not_cooccur=a.do_not_cooccur)
-    if a.metrics:
-        from . import runtime
-        m = {"verb": a.verb, "seconds": round(time.perf_counter() - t_begin, 4)}
-        if isinstance(res, dict):
-            m.update(frames=res.get("frames"), tracks=len(res.get("tracks", ())), faces=int(len(res["face_T"])) if "face_T" in res else None,
-                     clusters=len(set(res["labels"].values())) if res.get("labels") else None, peak_frames_resident=res.get("peak_frames_resident"),
-                     stage_seconds={k: round(v, 4) for k, v in res.get("timings", {}).items()})
-        try:
-            free, total = (ctx or runtime.default_context()).mem_info()
-            m["device_memory_in_use_bytes"] = total - free
-        except Exception:          # noqa: BLE001 -- the figure is optional
-            pass
-        with open(a.metrics, "w") as f:
-            json.dump(m, f, indent=1)
-    return 0
+    return res
 
 
 if __name__ == "__main__":

@@ -2,22 +2,15 @@
 windows of a film go through runtime.Context.frame_hist in batches, the file, and how `link` scores pairs of tracks, finds the mutual
 best matches and merges a label file along them.  Everything is integer arithmetic but the one float-to-int rule, `half_up`.  Nothing
 here touches the device but `measure`."""
-import math
-
 import numpy as np
 
-from .talk import ms
+from .talk import half_up, ms             # half_up: the float-to-int rule of both verbs (CLOTHES.md)
 
 BINS = 256                               # PVF_HIST_BINS
 MAX_BANDS = 4                            # PVF_HIST_MAX_BANDS
 MAX_WINDOWS = 65536                      # PVF_HIST_MAX_WINDOWS: windows of one library call
 HEAD = 6                                 # track, first ms, last ms, faces used, faces skipped, bands
 ONE = 65536                              # the unit of scores and thresholds
-
-
-def half_up(x):
-    """the float-to-int rule of both verbs: floor(x + 1/2), x the float64 product or fraction as Python computes it"""
-    return int(math.floor(float(x) + 0.5))
 
 
 def torso(box, widen=0.5, drop=0.25, height=2.0):

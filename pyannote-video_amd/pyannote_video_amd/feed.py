@@ -1,9 +1,46 @@
 """`FrameFeed`: the chosen frames of a video, read in a thread of their own and staged in HBM ahead of the thread that computes on them.
-What the verbs that read some frames of a film share (cli.py: extract, faces, talk, tube, demo / redact); the verbs that read every frame
-and cut it into shots go through engine.StreamSource."""
+What the verbs that read some frames of a film share (cli.py: extract, faces, talk, tube, clothes, demo / redact and storyboard.build) and,
+with `EveryKth` as the chosen frames and `frame_range` as its bounds, the verbs that measure every frame (fingerprint, blend, motion,
+text); all but clothes and demo / redact take the frames a library call's worth at a time (`FrameFeed.batches`).  The verbs that read every
+frame and cut it into shots go through engine.StreamSource."""
 import queue
 import threading
 from .runtime import HostFrameStager
+
+
+def frame_range(video, t_from=0.0, t_until=None):
+    """(first, end): the frames of `video` whose time index / frame_rate lies in [t_from, t_until), cut at the video's length; end is None
+    for a stream, which has no length, without t_until: as far as it goes"""
+    rate = float(video.frame_rate)
+    first = 0
+    while first / rate < t_from:
+        first += 1
+    end = None
+    if t_until is not None:
+        end = first
+        while end / rate < t_until:
+            end += 1
+    try:
+        end = len(video) if end is None else min(end, len(video))
+    except TypeError:
+        pass
+    return first, end
+
+
+class EveryKth(object):
+    """the `wanted` of a FrameFeed that wants every k-th frame from `first` on, below `end`, whatever the video's length"""
+
+    def __init__(self, first=0, end=None, k=1):
+        self.first, self.end, self.k = int(first), (1 << 40 if end is None else int(end)), int(k)
+
+    def __contains__(self, i):
+        return self.first <= i < self.end and (i - self.first) % self.k == 0
+
+    def __iter__(self):                  # (the feed reads up to max(wanted))
+        return iter((self.first + (len(self) - 1) * self.k,))
+
+    def __len__(self):
+        return max((self.end - self.first + self.k - 1) // self.k, 0)
 
 
 class FrameFeed(object):
@@ -68,6 +105,20 @@ class FrameFeed(object):
                 self._raise_reader_error()
                 return
             yield item
+
+    def batches(self, size, weight=None):
+        """the same frames as lists of (index, device frame), a library call's worth each: a list is closed by the frame that brings the
+        sum of weight(index) -- 1 a frame without `weight` -- to `size` or more; what is left at the end is the last, shorter list.
+        Nothing is released here: the caller gives back what its call is done with."""
+        part, held = [], 0
+        for item in self:
+            part.append(item)
+            held += 1 if weight is None else weight(item[0])
+            if held >= size:
+                yield part
+                part, held = [], 0
+        if part:
+            yield part
 
     def _raise_reader_error(self):
         e, self.error = self.error, None

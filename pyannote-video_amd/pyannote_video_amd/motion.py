@@ -4,17 +4,13 @@ Nothing here touches the device but `Pairs.measure`, which calls runtime.Context
 import numpy as np
 
 from .storyboard import tile_size        # noqa: F401 -- th follows from --width as a storyboard thumbnail's does
-from .talk import ms
+from .talk import half_up, ms
 
 WORDS = 10
 MIN_SIDE, MAX_SIDE, MAX_PIXELS = 12, 256, 16384          # PVF_MOTION_MIN_SIDE, _MAX_SIDE, _MAX_PIXELS
 MOVES = ("pan-left", "pan-right", "tilt-up", "tilt-down", "zoom-in", "zoom-out")
 KINDS = MOVES + ("static",)
 LOW32 = 0xFFFFFFFF
-
-
-def half_up(x):
-    return int(np.floor(float(x) + 0.5))
 
 
 def div_half_up(a, b):
@@ -44,18 +40,18 @@ class Pairs(object):
         self.held = None                         # the frame in front of the next batch
 
     def measure(self, frames):
-        """-> (rows int64 [len(frames), 10], the frame the caller may release now, or None).  The first frame of the video gets a row
-        without valid pixels."""
+        """-> (rows int64 [len(frames), 10], the frames the caller may release now: the one held from before and all but the last of
+        these).  The first frame of the video gets a row without valid pixels."""
         if not frames:
-            return np.zeros((0, WORDS), np.int64), None
+            return np.zeros((0, WORDS), np.int64), []
         chain = ([self.held] if self.held is not None else []) + list(frames)
         rows, _ = self.ctx.shot_motion(chain, self.tw, self.th, self.tables)
         if self.held is None:
             head = np.zeros((1, WORDS), np.int64)
             head[0, 9] = self.tw | self.th << 16
             rows = np.concatenate([head, rows])
-        done, self.held = self.held, frames[-1]
-        return rows, done
+        self.held = chain[-1]
+        return rows, chain[:-1]
 
 
 def load(path, who="camera"):

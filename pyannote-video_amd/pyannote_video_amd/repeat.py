@@ -2,26 +2,17 @@
 matching prints (runtime.Context.print_runs) become segments, and what is written.  Nothing here touches the device."""
 import numpy as np
 
+from .feed import EveryKth
 from .talk import ms
 
 RUNS_STRIP = 1024                        # PVF_RUNS_STRIP: rows of A a workgroup of print_runs_k walks
 MAX_ROWS = 1 << 24                       # PVF_PRINT_MAX_ROWS
 
 
-class EveryFrame(object):
-    """the `wanted` of a FrameFeed that wants every frame of a video, whatever its length: the frames whose index lies in [first, end)"""
-
-    def __init__(self, first=0, end=None):
-        self.first, self.end = int(first), (MAX_ROWS if end is None else int(end))
-
-    def __contains__(self, i):
-        return self.first <= i < self.end
-
-    def __iter__(self):                  # (the feed reads up to max(wanted))
-        return iter((self.end - 1,))
-
-    def __len__(self):
-        return max(self.end - self.first, 0)
+def EveryFrame(first=0, end=None):
+    """the `wanted` of a FrameFeed that wants every frame of a video, whatever its length: the frames whose index lies in [first, end),
+    at most as many as a print file holds"""
+    return EveryKth(first, MAX_ROWS if end is None else end, 1)
 
 
 def stamp(prints, first, frame_rate):

@@ -184,20 +184,10 @@ def build(ctx, video, shots, labels=None, per=1, width=160, columns=None, by="ti
     thumb_of = {}
     with FrameFeed(ctx, video, set(wanted), ahead=ahead if ahead is not None else batch + 32, ring_depth=max(2, min(len(wanted), 16)),
                    seek=True, name="pvface-storyboard-reader") as feed:
-        pend_f, pend_i = [], []
-
-        def flush():
-            if pend_i:
-                got = ctx.frame_thumbs(pend_f, tw, th)
-                for fi, t in zip(pend_i, got):
-                    thumb_of[fi] = t
-            feed.release_all(pend_f)
-            del pend_f[:], pend_i[:]
-        for fi, dev in feed:
-            pend_f.append(dev); pend_i.append(fi)
-            if len(pend_i) >= batch:
-                flush()
-        flush()
+        for part in feed.batches(batch):
+            frames = [dev for _, dev in part]
+            thumb_of.update(zip((fi for fi, _ in part), ctx.frame_thumbs(frames, tw, th)))
+            feed.release_all(frames)
     thumbs = np.stack([thumb_of[chosen[ci][3][k]] for ci, k in tiles]).reshape(-1, th, tw, 3)
     sheet = ctx.thumb_sheet(thumbs, [corners[ci][k] for ci, k in tiles], W, H, BACKGROUND, prims)
     lines = [index_line(chosen[ci][0], k, chosen[ci][3][k], fps, corners[ci][k], chosen[ci][2]) for ci, k in tiles]

@@ -21,6 +21,11 @@ def ms(t):
     return int(round(float(t) * 1000.0))
 
 
+def half_up(x):
+    """the float-to-int rule of the verbs' options: floor(x + 1/2), x the float64 product or fraction as Python computes it"""
+    return int(math.floor(float(x) + 0.5))
+
+
 def openness(pts):
     """sqrt(gap^2 / width^2) from the 68 integer points: the inner lips' middle points (62 over 66) against the mouth corners (48, 54);
     0.0 when the corners coincide"""

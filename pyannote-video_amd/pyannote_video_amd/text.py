@@ -4,17 +4,14 @@ components over time and space, four drop rules, and the tracks on screen with a
 touches the device but `Carry.measure`, which calls runtime.Context.frame_text."""
 import numpy as np
 
-from .talk import ms
+from .feed import EveryKth               # noqa: F401 -- which frames of a video are measured: every k-th from the first
+from .talk import half_up, ms
 
 CELL = 16                                # PVF_TEXT_CELL
 HEAD = 8                                 # PVF_TEXT_HEAD_WORDS
 MAX_SIDE = 8192                          # PVF_TEXT_MAX_SIDE
 MAX_FRAMES = 4096                        # PVF_TEXT_MAX_FRAMES: frames of one library call
 HAS_PREV = 1 << 31
-
-
-def half_up(x):
-    return int(np.floor(float(x) + 0.5))
 
 
 def geometry(w, h):
@@ -31,22 +28,6 @@ def row_words(w, h):
 def every(step, frame_rate):
     """k of `--step`: every k-th frame is measured, k = max(1, floor(step * rate + 1 / 2))"""
     return max(1, half_up(float(step) * float(frame_rate)))
-
-
-class EveryKth(object):
-    """the `wanted` of a FrameFeed that wants every k-th frame from `first` on, below `end`, whatever the video's length"""
-
-    def __init__(self, first=0, end=None, k=1):
-        self.first, self.end, self.k = int(first), (1 << 40 if end is None else int(end)), int(k)
-
-    def __contains__(self, i):
-        return self.first <= i < self.end and (i - self.first) % self.k == 0
-
-    def __iter__(self):                  # (the feed reads up to max(wanted))
-        return iter((self.first + (len(self) - 1) * self.k,))
-
-    def __len__(self):
-        return max((self.end - self.first + self.k - 1) // self.k, 0)
 
 
 def stamp(rows, first, frame_rate, k=1):
@@ -69,11 +50,13 @@ class Carry(object):
         self.held = None                         # the frame in front of the next batch
 
     def measure(self, frames):
-        """-> (rows uint32 [len(frames), 8 + ch wpr], the frame the caller may release now, or None)"""
+        """-> (rows uint32 [len(frames), 8 + ch wpr], the frames the caller may release now: the one held from before and all but the
+        last of these)"""
         if not frames:
-            return None, None
+            return None, []
         rows, _ = self.ctx.frame_text(frames, prev=self.held, edge=self.edge, still=self.still, on=self.on)
-        done, self.held = self.held, frames[-1]
+        done = ([self.held] if self.held is not None else []) + list(frames[:-1])
+        self.held = frames[-1]
         return rows, done
 
 

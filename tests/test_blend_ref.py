@@ -281,16 +281,18 @@ class Ring(object):
 
 
 class ScriptContext(object):
-    """frame_blend is the restatement"""
+    """frame_blend is the restatement; given: every frame an earlier call was given -- planes are carried, no frame is"""
 
     def __init__(self):
-        self.live, self.calls = [], []
+        self.live, self.calls, self.given = [], [], []
 
     def ingest_ring(self, h, w, depth=16):
         return Ring(self)
 
     def frame_blend(self, frames, tw, th, hist=None, want_luma=True):
         assert all(not f.released for f in frames), "a row asked of a released frame"
+        assert all(f.released for f in self.given), "a frame of an earlier call is still resident"
+        self.given.extend(frames)
         self.calls.append((len(frames), 0 if hist is None else len(hist)))
         return br.frame_rows([f.rgb for f in frames], tw, th, hist=hist)
 
@@ -349,6 +351,22 @@ def test_both_verbs_through_main_equal_the_plain_loop(tmp_path, scripted, clip):
     part = np.load(files[1])
     assert np.array_equal(part, br.video_rows(c.frames[10:50], 32, 18, 25.0, first=10)) and part[0, 13] == 10 and part[0, 12] == 400
     assert cli.main(["transition", "--move", "8", "--linear", "0.1", "--flat", "1", "--min-duration", "0.3", files[7], "-"]) == 0
+
+
+def test_the_carrier_hands_back_every_frame_it_was_given(clip):
+    """measure -> (rows, the frames the caller may release now): all of them; ScriptContext checks at every call that none is left"""
+    ctx = ScriptContext()
+    carry = blend.Carry(ctx, 32, 18)
+    frames = [Dev(f) for f in clip[0].frames[:7]]
+    parts = []
+    for part in (frames[:3], frames[3:6], frames[6:]):
+        rows, done = carry.measure(part)
+        assert len(rows) == len(part) and sorted(map(id, done)) == sorted(map(id, part))
+        parts.append(rows)
+        for f in done:
+            f.release()
+    assert ctx.calls == [(3, 0), (3, 3), (1, 6)] and all(f.released for f in frames)
+    assert np.array_equal(np.concatenate(parts), br.frame_rows(clip[0].frames[:7], 32, 18)[0])
 
 
 def test_a_stream_without_a_length_and_the_arguments(tmp_path, clip):

@@ -1,6 +1,7 @@
 """CPU: feed.FrameFeed -- the reader thread, bounded queue, pinned ring and frame ownership that the verbs reading chosen frames share
 (cli.py: extract, faces, talk, tube, demo / redact) -- on a scripted video and ring: order and filter, seeking, the bound on what is
 staged ahead, whose error comes out, and that every frame the feed staged is given back exactly once however the block is left.  Then
+FrameFeed.batches, the lists the verbs make one library call on: by frame count, by weight, with a failing reader, left early.  Then
 cli._render_plan (the body of demo and redact) on a scripted egress ring: one picture per plan entry, in plan order."""
 import threading
 
@@ -220,6 +221,62 @@ def test_release_is_safe_to_repeat_and_ignores_foreign_frames():
         feed.release(None)
         assert [d.released for d in devs] == [True, True, False, False] and not foreign.released
     assert settled(ctx, threading.active_count()) and not foreign.released
+
+
+# ---- FrameFeed.batches: the same frames, a library call's worth at a time ----
+@pytest.mark.parametrize("n,size", [(0, 4), (3, 4), (8, 4), (9, 4), (5, 1)])
+def test_batches_by_frame_count(n, size):
+    threads = threading.active_count()
+    ctx, parts = Context(), []
+    with FrameFeed(ctx, Video(n), set(range(n)), ahead=2) as feed:
+        for part in feed.batches(size):
+            assert part and all(dev.i == fi and not dev.released for fi, dev in part)
+            parts.append([fi for fi, _ in part])
+            feed.release_all(dev for _, dev in part)
+    assert [len(p) for p in parts] == [size] * (n // size) + ([n % size] if n % size else [])
+    assert [fi for p in parts for fi in p] == list(range(n))
+    assert settled(ctx, threads)
+
+
+@pytest.mark.parametrize("weights,want", [((1, 3, 2, 5, 1, 1), [[0, 1], [2, 3], [4, 5]]),       # closed by the frame that brings the sum to 4
+                                          ((5, 1, 3, 9, 2), [[0], [1, 2], [3], [4]])])          # a frame heavier than the size: a list of its own
+def test_batches_by_weight(weights, want):
+    threads = threading.active_count()
+    ctx, parts, asked = Context(), [], []
+
+    def weight(fi):
+        asked.append(fi)
+        return weights[fi]
+    with FrameFeed(ctx, Video(len(weights)), set(range(len(weights))), ahead=2) as feed:
+        for part in feed.batches(4, weight):
+            parts.append([fi for fi, _ in part])
+            assert not any(dev.released for _, dev in part)                         # nothing is released on the way: the caller does
+    assert parts == want and asked == list(range(len(weights)))
+    assert settled(ctx, threads)
+
+
+def test_batches_raise_an_error_of_the_reader_where_they_end():
+    threads = threading.active_count()
+    ctx, parts = Context(), []
+    with FrameFeed(ctx, Video(12, fail_at=7), set(range(12)), ahead=2) as feed:
+        with pytest.raises(IOError, match="scripted decode error"):
+            for part in feed.batches(3):
+                parts.append([fi for fi, _ in part])
+        assert parts == [[0, 1, 2], [3, 4, 5]]                                      # the lists in front of it; frame 6 was in no list
+        assert not any(d.released for d in ctx.frames)
+    assert len(ctx.frames) == 7 and settled(ctx, threads)
+
+
+def test_leaving_the_batches_early_gives_everything_back():
+    threads = threading.active_count()
+    ctx = Context()
+    with FrameFeed(ctx, Video(50), set(range(50)), ahead=4) as feed:
+        for part in feed.batches(4):
+            assert [fi for fi, _ in part] == [0, 1, 2, 3]
+            feed.release(part[0][1])                                                # one given back here, the rest kept
+            break
+    assert 4 <= len(ctx.frames) < 50
+    assert settled(ctx, threads)                                                    # (Dev.release asserts that it is called once)
 
 
 # ---- cli._render_plan: the feed in front, the egress ring and the writer thread behind ----

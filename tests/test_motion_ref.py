@@ -235,10 +235,11 @@ class Ring(object):
 
 
 class ScriptContext(object):
-    """shot_motion is the oracle's flow and the restatement's rows, one pair at a time"""
+    """shot_motion is the oracle's flow and the restatement's rows, one pair at a time; given: every frame an earlier call was given --
+    its last is carried as the first of the next, no other"""
 
     def __init__(self):
-        self.live, self.calls, self.known = [], [], {}
+        self.live, self.calls, self.known, self.given = [], [], {}, []
 
     def ingest_ring(self, h, w, depth=16):
         return Ring(self)
@@ -246,6 +247,8 @@ class ScriptContext(object):
     def shot_motion(self, frames, width, height, tables, want_dfd=True):
         from oracle import oracle
         assert all(not f.released for f in frames), "a row asked of a released frame"
+        assert all(f.released for f in self.given if f is not frames[0]), "a frame of an earlier call, not the carried one, is still resident"
+        self.given.extend(frames)
         self.calls.append(len(frames))
         rows = []
         for a, b in zip(frames[:-1], frames[1:]):
@@ -336,6 +339,25 @@ def test_motion_through_main_equals_the_plain_loop_at_every_batch(tmp_path, monk
                  ["motion", "--width", "300", "film", bad], ["transition", "--motion", bad, bad, out]):
         with pytest.raises(SystemExit):
             cli.main(args)
+
+
+def test_the_carrier_hands_back_all_but_the_frame_it_carries(clip):
+    """measure -> (rows, the frames the caller may release now): the one held from before and all but the last of the call's;
+    ScriptContext checks at every call that no other is left"""
+    c, want = clip
+    ctx = ScriptContext()
+    carry = motion.Pairs(ctx, 96, 54)
+    frames = [Dev(f) for f in c.frames[:7]]
+    parts, held = [], []
+    for part in (frames[:3], frames[3:6], frames[6:]):
+        rows, done = carry.measure(part)
+        assert len(rows) == len(part) and sorted(map(id, done)) == sorted(map(id, held + part[:-1]))
+        parts.append(rows)
+        for f in done:
+            f.release()
+        held = part[-1:]
+    assert ctx.calls == [3, 4, 2] and [f.released for f in frames] == [True] * 6 + [False] and carry.held is frames[6]
+    assert np.array_equal(np.concatenate(parts)[:, :8], want[:7, :8])                # (word 8 is the verb's stamp)
 
 
 def test_transition_with_motion_takes_the_soft_pan_out_of_the_dissolves(tmp_path):

@@ -308,16 +308,19 @@ def test_a_moving_background_without_a_strap_gives_nothing():
 
 # ---- the verbs --------------------------------------------------------------------------------------------------------------------------
 class ScriptContext(object):
-    """frame_text is the restatement, one call at a time"""
+    """frame_text is the restatement, one call at a time; given: every frame an earlier call was given -- its last is carried as `prev`
+    of the next, no other"""
 
     def __init__(self):
-        self.live, self.calls = [], []
+        self.live, self.calls, self.given = [], [], []
 
     def ingest_ring(self, h, w, depth=16):
         return Ring(self)
 
     def frame_text(self, frames, prev=None, edge=48, still=8, on=24, want_counts=False):
         assert all(not f.released for f in frames) and (prev is None or not prev.released), "a row asked of a released frame"
+        assert all(f.released for f in self.given if f is not prev), "a frame of an earlier call, not the carried one, is still resident"
+        self.given.extend(frames)
         self.calls.append((len(frames), prev is not None))
         rows, counts = tr.rows_of([f.rgb for f in frames], None if prev is None else prev.rgb, edge, still, on)
         return rows, (counts if want_counts else None)
@@ -364,6 +367,25 @@ def test_text_through_main_equals_the_plain_loop_at_every_batch_and_step(tmp_pat
                  ["--step", "-1"]):
         with pytest.raises(SystemExit):
             cli.main(["text"] + args + ["film", out])
+
+
+def test_the_carrier_hands_back_all_but_the_frame_it_carries():
+    """measure -> (rows, the frames the caller may release now): the one held from before and all but the last of the call's;
+    ScriptContext checks at every call that no other is left"""
+    clip = tc.planted_clip()[20:27]
+    ctx = ScriptContext()
+    carry = text.Carry(ctx)
+    frames = [Dev(f) for f in clip]
+    parts, held = [], []
+    for part in (frames[:3], frames[3:6], frames[6:]):
+        rows, done = carry.measure(part)
+        assert len(rows) == len(part) and sorted(map(id, done)) == sorted(map(id, held + part[:-1]))
+        parts.append(rows)
+        for f in done:
+            f.release()
+        held = part[-1:]
+    assert ctx.calls == [(3, False), (3, True), (1, True)] and [f.released for f in frames] == [True] * 6 + [False] and carry.held is frames[6]
+    assert np.array_equal(np.concatenate(parts), tr.rows_of(clip, None, 48, 8, 24)[0])
 
 
 def test_the_wanted_set_and_the_stamp():
