@@ -778,6 +778,14 @@ int32_t pvf_debug_conv(pvf_handle ctx, const int32_t geom[18], const float* in, 
                        const float* beta, const float* skip, int32_t split, int32_t force_generic, float* out, int32_t* flags);
 /* head_k on x [n][hw][256] with the loaded model's 256 x 128 matrix: out [n][128] */
 int32_t pvf_debug_embed_head(pvf_handle ctx, const float* x, int32_t n, int32_t hw, float* out);
+/* The scratch arenas of the context (grow-only device buffers that the kernel families carve their intermediates from, several families
+ * per arena).  report: one line "name capacity_in_bytes" per arena, NUL-terminated text; an arena that holds state across calls (the
+ * detector's feature maps with their zero border, the resident ORB sets) has " state" behind its size.  *need is always the bytes of
+ * the text with its NUL; the text is written only when cap >= *need (call again with that room; report may be NULL with cap 0).
+ * fill = -1: report only.  fill = 0..255: both streams of the context are synchronised, the whole capacity of every arena that holds NO
+ * state is set to that byte, and the device is synchronised again -- what a call then finds under its layout is what another family
+ * could have left there.  Any other fill is refused before any work. */
+int32_t pvf_debug_scratch(pvf_handle ctx, int32_t fill, char* report, int64_t cap, int64_t* need);
 
 /* ---- f4: shot boundary detection ------------------------------------------------------------------
  * ref: pyannote/video/structure/shot.py:71-73 (_convert: RGB -> gray -> cv2.resize to `width` x `height`), :75-99 (dfd: Farneback flow

@@ -582,6 +582,78 @@ extern "C" int32_t pvf_mem_info(pvf_handle h, int64_t* free_bytes, int64_t* tota
     API_END
 }
 
+// ---------------------------------------------------------------------------------------------------
+// The scratch arenas of a context (the DevBuf members of Ctx), one row each.  call_local: no entry reads from the arena anything an
+// earlier entry wrote -- every call uploads, zeroes or computes what it reads -- so pvf_debug_scratch may fill it with any byte between
+// two calls.  An arena that holds state across calls is reported and never filled; the comment says what lives there.
+namespace {
+struct ArenaRow { const char* name; DevBuf* buf; bool call_local; };
+std::vector<ArenaRow> arena_table(Ctx* c)
+{
+    return {
+        {"s_grad", &c->s_grad, true},             // fhog_device: gradients of one call
+        {"s_pyr", &c->s_pyr, true},               // the detector's image pyramid (rebuilt by every entry that reads it), pvf_debug_fhog's image
+        {"s_hist", &c->s_hist, true},
+        {"s_norm", &c->s_norm, true},
+        // STATE: the zero border of the detector's feature maps.  feat_ring_zero_k writes it once per plan (feat_ring_owner) and every
+        // later batch of that plan scores on it without writing it again.
+        {"s_feat", &c->s_feat, false},
+        {"s_cand", &c->s_cand, true},             // counts and control words are zeroed by every call
+        {"s_cand2[0]", &c->s_cand2[0], true},
+        {"s_cand2[1]", &c->s_cand2[1], true},
+        {"s_fptr[0]", &c->s_fptr[0], true},       // frame pointers, uploaded by every batch
+        {"s_fptr[1]", &c->s_fptr[1], true},
+        {"s_screen", &c->s_screen, true},         // the screening list; its length lives in s_cand's control words
+        {"s_misc", &c->s_misc, true},
+        {"s_chip", &c->s_chip, true},
+        {"s_chip_pyr", &c->s_chip_pyr, true},
+        {"s_act0", &c->s_act0, true},
+        {"s_act1", &c->s_act1, true},
+        {"s_act2", &c->s_act2, true},
+        {"s_trk0", &c->s_trk0, true},
+        // the tracker's filters live in Tracker::d_state, and a deferred update is redone in full at its commit (dsst_update_many mode 2):
+        // no computation reads these again.  pvf_debug_tracker_state copies its F out of s_trk1 -- a look at what the LAST tracker call
+        // left, meaningful only right behind that call; a fill in between shows there, as it should
+        {"s_trk1", &c->s_trk1, true},
+        {"s_trk2", &c->s_trk2, true},
+        {"s_trkfeat", &c->s_trkfeat, true},
+        {"s_clu0", &c->s_clu0, true},
+        {"s_clu1", &c->s_clu1, true},             // a distance matrix stays here for the agglomeration / the decision of the SAME entry only
+        {"s_emb_flags", &c->s_emb_flags, true},   // zeroed before every split forward
+        {"s_emb_redo", &c->s_emb_redo, true},
+        {"s_jit", &c->s_jit, true},
+        // STATE: keypoints, descriptors and counts of the last pvf_orb_extract, which pvf_orb_match_counts reads when it is given none
+        {"s_orb_set", &c->s_orb_set, false},
+        {"s_orb_work", &c->s_orb_work, true},     // the matcher uploads its pairs (and sets) per call
+    };
+}
+}  // namespace
+
+// tests only: the arenas' capacities as text, and (fill 0..255) that byte over the whole capacity of every call-local arena
+extern "C" int32_t pvf_debug_scratch(pvf_handle h, int32_t fill, char* report, int64_t cap, int64_t* need)
+{
+    API_BEGIN
+    Ctx* c = pvf_ctx(h);
+    PVF_REQUIRE(fill >= -1 && fill <= 255, "pvf_debug_scratch: fill is a byte 0..255, or -1 to report only");
+    PVF_REQUIRE(cap >= 0 && need && (report || cap == 0), "pvf_debug_scratch: a report buffer of cap bytes (or none, cap 0) and a place for the size");
+    std::lock_guard<std::recursive_mutex> det_lock(c->det_mu);
+    std::lock_guard<std::recursive_mutex> api_lock(c->api_mu);
+    HIP_CHECK(hipSetDevice(c->device));
+    const std::vector<ArenaRow> rows = arena_table(c);
+    if (fill >= 0) {
+        HIP_CHECK(hipStreamSynchronize(c->det_stream));
+        HIP_CHECK(hipStreamSynchronize(c->stream));
+        for (const ArenaRow& r : rows)
+            if (r.call_local && r.buf->p && r.buf->cap) HIP_CHECK(hipMemset(r.buf->p, fill, r.buf->cap));
+        HIP_CHECK(hipDeviceSynchronize());
+    }
+    std::string text;
+    for (const ArenaRow& r : rows) text += std::string(r.name) + " " + std::to_string(r.buf->cap) + (r.call_local ? "" : " state") + "\n";
+    *need = (int64_t)text.size() + 1;
+    if (cap >= *need) memcpy(report, text.c_str(), text.size() + 1);
+    API_END
+}
+
 extern "C" int32_t pvf_prof_enable(pvf_handle h, int32_t on)
 {
     API_BEGIN

@@ -180,6 +180,7 @@ _SIGS = {
     "pvf_debug_embed_stage": (C.c_int32, [H, P, C.c_int32, C.c_int32, C.c_int32, P, P, P]),
     "pvf_debug_conv": (C.c_int32, [H, P, P, P, P, P, P, P, C.c_int32, C.c_int32, P, P]),
     "pvf_debug_embed_head": (C.c_int32, [H, P, C.c_int32, C.c_int32, P]),
+    "pvf_debug_scratch": (C.c_int32, [H, C.c_int32, P, C.c_int64, P]),
     "pvf_shot_dfd": (C.c_int32, [H, P, C.c_int32, C.c_int32, C.c_int32, P, P, P, P]),
     "pvf_orb_extract": (C.c_int32, [H, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P, P, P]),
     "pvf_orb_match_counts": (C.c_int32, [H, P, P, C.c_int32, C.c_int32, P, C.c_int64, P]),

@@ -962,6 +962,25 @@ class Context(object):
         check(self._l.pvf_debug_embed_head(self._h, ptr(x), n, hw, ptr(out)))
         return out
 
+    def scratch(self, fill=None, state=False):
+        """{arena: capacity in bytes} of the context's scratch arenas (pvf_debug_scratch).  fill = 0..255: first set every byte of every
+        arena that holds no state across calls to that value (tests: what a call finds under its layout is then another family's
+        leftovers, not a fresh allocation's zeros).  state=True: (sizes, the set of arenas that hold state and are never filled)."""
+        need = C.c_int64(0)
+        check(self._l.pvf_debug_scratch(self._h, -1 if fill is None else int(fill), None, 0, C.byref(need)))
+        while True:
+            buf = np.zeros(need.value, np.uint8)
+            check(self._l.pvf_debug_scratch(self._h, -1, ptr(buf), buf.nbytes, C.byref(need)))
+            if need.value <= buf.nbytes:
+                break
+        sizes, held = {}, set()
+        for line in buf.tobytes().split(b"\0")[0].decode().splitlines():
+            tok = line.split()
+            sizes[tok[0]] = int(tok[1])
+            if tok[2:] == ["state"]:
+                held.add(tok[0])
+        return (sizes, held) if state else sizes
+
     # ---- f4: shot boundary detection
     def shot_dfd(self, frames, width, height, tables, want_gray=False, want_flow=False):
         """displaced frame differences of consecutive frames (structure/shot.py:71-99): float64 [n - 1]

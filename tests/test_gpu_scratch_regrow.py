@@ -1,6 +1,7 @@
 """GPU: the order the rest of the suite does not run -- scratch buffers that start EMPTY, grow, and are carved again for a smaller call
 and by another subsystem (csrc/scratch_layout.h sizes and carves them; `s_misc` alone is shared by the agglomeration, the landmarks, ORB
-extraction and the shot detector).  The session context has usually grown every buffer to its largest case before a small one runs, so
+extraction, the shot detector and the decision of `identify`; tests/test_gpu_scratch_sharers.py runs every sharer of every buffer behind
+every other).  The session context has usually grown every buffer to its largest case before a small one runs, so
 this file opens a context of its own.  Every step is compared with the reference the entry's own tests use, with their equality: the
 oracle (the agglomeration on the device's matrix bit for bit, the matrix itself to 1e-12 relative), tests/cooccur_ref.py, tests/orb_ref.py
 (bit for bit).  The matrices the references start from are computed on the SESSION context, which leaves the buffers under test alone."""
@@ -92,6 +93,17 @@ def _shot_step(own, oracle, tables, frames):
         assert dfd[i - 1] == oracle.shot_dfd(small[i - 1], small[i], tables)
 
 
+def _identify_step(own):
+    """the fifth user of s_misc: the decision per group (identify_pick_k) carves its four result arrays there"""
+    from tests import identify_ref
+    from tests.scratch_cases import TOL
+    X, rs, G, gs = identify_ref.main_case()
+    best, bd, second, sd, D = own.identify(X, rs, G, gs, 0.6, return_dist=True)
+    assert np.allclose(D, identify_ref.mean_dist(X, rs, G, gs), **TOL[0])
+    assert identify_ref.same_picks((best, bd, second, sd), identify_ref.pick(D, 0.6))
+    assert np.array_equal(best, identify_ref.main_case_truth())
+
+
 def test_s_misc_recarved_by_its_four_users_in_turn(own, ctx, oracle, small_video, model_paths):
     from pyannote_video_amd import models, structure
     sp = oracle.ShapePredictor(models.load_container(model_paths[0]))
@@ -104,6 +116,7 @@ def test_s_misc_recarved_by_its_four_users_in_turn(own, ctx, oracle, small_video
     n, nb = _cooccur_step(own, ctx, 65, seed=12)        # one 64 x 64 stamp tile plus one row
     assert n > 0 and nb > 0
     _landmark_step(own, sp, frame, boxes)
+    _identify_step(own)                                 # (a fifth user since the `identify` verb; behind the landmarks, in front of the flows)
     _shot_step(own, oracle, tables, clip[:2])
     _shot_step(own, oracle, tables, clip)
     X, rs, _ = R.make(3, seed=13)
