@@ -68,6 +68,50 @@ def chip_levels(rect, w, h, rows=CHIP, cols=CHIP):
     return dict(empty=False, levels=levels, sw=sw, sh=sh, collapsed=collapsed)
 
 
+def _rot(cx, cy, x, y, cs, sn):
+    dx, dy = x - cx, y - cy
+    return cs * dx - sn * dy + cx, sn * dx + cs * dy + cy
+
+
+def chip_plan(rect, w, h, rows=CHIP, cols=CHIP, cs=1.0, sn=0.0):
+    """chip_levels() for a rectangle turned by (cs, sn) about its centre, with what the kernels are handed: -> dict(empty, levels, sw, sh,
+    collapsed, x0, y0: the strip's first column and row in the frame, dims: [(width, height)] of the strip and of every pyramid level
+    built from it (a collapsed level is (0, 0)), m, b: the affine chip (column, row) -> sampled image, None for an empty plan).  Details
+    that are not finite make the empty plan.  The operations and their order are those of the library's host plan and the oracle's."""
+    out = dict(empty=True, levels=0, sw=0, sh=0, collapsed=False, x0=0, y0=0, dims=[], m=None, b=None)
+    if not all(math.isfinite(v) for v in tuple(rect) + (cs, sn)):
+        return out
+    size = float(rows * cols)
+    grow, r = 2.0, _down(rect)
+    while _area(r) > size:
+        r = _down(r)
+        grow = grow * 2 + 2
+    cx, cy = (rect[0] + rect[2]) / 2, (rect[1] + rect[3]) / 2
+    pts = [_rot(cx, cy, x, y, cs, sn) for x, y in ((rect[0], rect[1]), (rect[2], rect[1]), (rect[0], rect[3]), (rect[2], rect[3]))]
+    l, t = min(p[0] for p in pts) - grow, min(p[1] for p in pts) - grow
+    rr, b = max(p[0] for p in pts) + grow, max(p[1] for p in pts) + grow
+    l, t, rr, b = max(l, 0.0), max(t, 0.0), min(rr, w - 1.0), min(b, h - 1.0)
+    if l > rr or t > b:
+        return out
+    x0, y0, x1, y1 = (int(math.floor(v + 0.5)) for v in (l, t, rr, b))
+    sw, sh = x1 - x0 + 1, y1 - y0 + 1
+    if sw <= 0 or sh <= 0:
+        return out
+    levels, r = 0, (rect[0] - x0, rect[1] - y0, rect[2] - x0, rect[3] - y0)
+    while _area(_down(r)) > size:
+        r = _down(r)
+        levels += 1
+    dims, collapsed = [(sw, sh)], False
+    for _ in range(levels):
+        pw, ph = dims[-1]
+        dims.append((0, 0) if (ph <= 8 or pw <= 8) else ((pw - 3) // 2, (ph - 3) // 2))
+        collapsed = collapsed or dims[-1] == (0, 0)
+    lcx, lcy = (r[0] + r[2]) / 2, (r[1] + r[3]) / 2
+    tl, tr, bl = _rot(lcx, lcy, r[0], r[1], cs, sn), _rot(lcx, lcy, r[2], r[1], cs, sn), _rot(lcx, lcy, r[0], r[3], cs, sn)
+    m = ((tr[0] - tl[0]) / float(cols - 1), (bl[0] - tl[0]) / float(rows - 1), (tr[1] - tl[1]) / float(cols - 1), (bl[1] - tl[1]) / float(rows - 1))
+    return dict(empty=False, levels=levels, sw=sw, sh=sh, collapsed=collapsed, x0=x0, y0=y0, dims=dims, m=m, b=tl)
+
+
 def box_class(box, w, h):
     """the classes the table must cover, for one start box"""
     out = set()
